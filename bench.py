@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s of the red-black PatchMatch hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one whole reference view through the hot path: init + `iterations` x (black, red)
@@ -18,6 +18,11 @@ launcher (no WORLD_SIZE in the environment).
 
 Prints ONE JSON line on rank 0.  `value` is the whole-job aggregate (sum over GPUs); at N=1 it is
 the BASELINE.json per-GPU figure.
+
+A plain run does only what that line needs: set up, warm up, time the steps, write the outputs (--dump-outputs) and
+print.  Everything else -- quality against the analytic ground truth, the roofline figures, the extra legs (exhaustive
+schedule, fast and reference-order modes, other scenes, views in flight, host boundary, other configurations) and the CPU
+baselines -- runs only under --full (--no-extras / --no-cpu-baseline drop parts of it there).
 """
 import argparse
 import ctypes as C
@@ -41,6 +46,25 @@ def _exp_env(name, default):
     return os.environ.get(name, default)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dirname, arrays, budget, suffix=""):
+    """--dump-outputs: the per-pixel arrays a caller of the timed path receives (name -> array of shape (rows, cols, ...)),
+    float32, as DIR/<name><suffix>.npy.  Where together they exceed `budget` bytes, the same fixed, seeded sample of pixels
+    is taken from each (shape (k, ...)), and the pixels' flat indices are written beside them as pixel_index<suffix>.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n_pix = min(a.shape[0] * a.shape[1] for a in arrays.values())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        k = max(1, int(budget // (total / n_pix + 8)))  # (+ 8: the float64 index of the pixel)
+        idx = np.sort(np.random.default_rng(12345).choice(n_pix, size=k, replace=False))
+        arrays = {name: a.reshape((n_pix,) + a.shape[2:])[idx] for name, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), a)
 
 
 def algorithmic_bytes_per_sweep_launch(n_pixels, n_views):
@@ -248,15 +272,20 @@ def self_launch(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (whole reference views), >= 1")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C", help="workload: A, B, C (default, the metric's config) or D")
     ap.add_argument("--scene", default="smooth", choices=["smooth", "steps", "patchy"],
                     help="synthetic scene: smooth height field (default), depth steps + occluder + sensor noise, or the "
                          "smooth surface with 30 %% flat albedo and a periodic texture band")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (exhaustive schedule, "
-                    "second scene, host boundary)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: quality against the ground truth, "
+                    "roofline figures, the extra legs and the CPU baselines (a plain run measures the timed steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (exhaustive "
+                    "schedule, other modes, scenes and configurations, views in flight, host boundary)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's final maps as DIR/norm4.npy (rows x cols x 4: unit "
+                    "normal, depth) and DIR/cost.npy (rows x cols), float32; other ranks add _rank<r> to the names")
     ap.add_argument("--colour", action="store_true", help="-color_processing variant of the workload (T=float4)")
     ap.add_argument("--cols", type=int, default=0, help="experiments only: override the frame width")
     ap.add_argument("--rows", type=int, default=0, help="experiments only: override the frame height")
@@ -266,6 +295,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercise the rank plumbing only (CPU tests)")
     ap.add_argument("--oversubscribe", action="store_true", help="allow more ranks than GPUs (tests on a 1-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -364,9 +395,10 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         t = sess.solve(timing=True)  # returns after the last kernel's HIP event
-        hs_ms, hs_pushed = sess.launch_times()
-        half_sweeps.append(hs_ms)
-        group_ms.append(sess.group_times())
+        if args.full:  # (per-launch times of the step: the roofline figures)
+            hs_ms, hs_pushed = sess.launch_times()
+            half_sweeps.append(hs_ms)
+            group_ms.append(sess.group_times())
         sweep_ms.append(t.ms_sweep_avg)
         total_ms.append(t.ms_total)
         init_ms.append(t.ms_init)
@@ -389,119 +421,18 @@ def main():
                 "frac_within_1pct_of_gt": float((rel_ < 0.01).mean())}
 
     # quality vs the analytic ground truth (sanity: the solver reconstructs the surface)
-    quality = quality_of(sess, info)
-    final_default = sess.get_state()  # (finalized maps of the last timed solve: compared with the exhaustive schedule's below)
+    quality = quality_of(sess, info) if args.full else None
+    final_default = None
+    if args.full or args.dump_outputs:
+        final_default = sess.get_state()  # (finalized maps of the last timed solve: compared with the exhaustive schedule's below)
+    if args.dump_outputs:  # what runcuda() hands its caller: the final planes (unit normal, depth) and costs
+        dump_outputs(args.dump_outputs, {"norm4": final_default[0], "cost": final_default[1]}, DUMP_LIMIT_BYTES // world,
+                     "" if rank == 0 else "_rank%d" % rank)
     sess.close()
 
     if rank == 0:
         value = world * args.steps * n_pix / elapsed / 1e6
-        ms_half_sweep = float(np.mean(sweep_ms))
-        alg = algorithmic_bytes_per_sweep_launch(n_pix, n_views)
-        # The dominant kernel: the fused pixel-per-lane sweep kernel.  Every half-sweep after the
-        # column-per-lane / pushed ones is exactly one launch of it, timed by its own pair of HIP events on
-        # the library's stream (gipuma_hip_launch_times); the earlier half-sweeps (other kernels, push
-        # launches) only enter the per-view mean reported beside it.
-        hs = np.asarray(half_sweeps, dtype=np.float64)  # [steps][2 * iterations]
-        first_plain = 0
-        if hs.size:
-            cols_first = int(sched["cols_launches"])
-            first_plain = min(hs.shape[1], max(cols_first, hs_pushed))
-            if sched["group_from"] >= 0:  # the dominant kernel's half-sweeps: those of the plane-keyed propagation
-                first_plain = min(hs.shape[1], max(first_plain, sched["group_from"]))
-        dominant = hs[:, first_plain:] if hs.size and first_plain < hs.shape[1] else None
-        ms_launch = float(dominant.mean()) if dominant is not None else ms_half_sweep
-        # Where the propagation costs of a half-sweep come from pm::group_kernel (pm_group.h: box 15 on frames of
-        # >= 1024 tiles, from the fifth half-sweep on), a half-sweep is TWO launches -- that kernel (the cost
-        # evaluations of the reference's close + far kernels) and the fused sweep launch (their accept tests replayed
-        # + the refinement kernel) -- and the former is the dominant kernel by time.  It is timed by its own pair of
-        # HIP events on the library's stream (gipuma_hip_group_times); its algorithmic bytes are the close + far
-        # share of SURVEY 8d's per-launch figure: (28 + 28) B of state and 2 x 4 (N + 1) B of images per active pixel.
-        gm = np.asarray(group_ms, dtype=np.float64) if group_ms and len(group_ms[0]) else np.zeros((0, 0))
-        dom_is_group = bool(gm.size and (gm > 0).any())
-        dom_name, dom_pmc_file = "pm::sweep_kernel", "pmc_latest_sweep_kernel.json"
-        dom_is_fused = bool(sched["group_from"] >= 0 and sched["group_fused"])
-        if dom_is_fused:  # one launch per half-sweep: propagation per plane + accept replay + refinement
-            dom_name, dom_pmc_file = "pm::sweep_group_kernel", "pmc_latest_sweep_group_kernel.json"
-        ms_sweep_launch = ms_launch
-        if dom_is_group:
-            used = gm > 0
-            ms_group_launch = float(gm[used].mean())
-            ms_sweep_launch = float((hs - gm)[used].mean())  # the fused sweep launch of the same half-sweeps
-            alg_half_sweep, ms_pair = alg, ms_launch
-            alg = n_pix * (56 + 8 * (n_views + 1)) / 2.0
-            alg_sweep = n_pix * (20 + 4 * (n_views + 1)) / 2.0
-            ms_launch = ms_group_launch
-            dom_name, dom_pmc_file = "pm::group_kernel", "pmc_latest_group_kernel.json"
-        achieved = alg / (ms_launch * 1e-3) / 1e9
-        # HBM-side bytes per sweep launch and VALU instruction counts are NOT measured in this run: they
-        # come from the PMC passes of the same command (scripts/pmc_passes.sh -> profiles/pmc_latest.json),
-        # FETCH_SIZE x2 (gfx950 correction, MI355X_MICROARCH.md HBM section) + WRITE_SIZE, separate --pmc
-        # passes; the object says so
-        pj = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc) and args.config == "C" and args.scene == "smooth" and not args.colour:
-            try:
-                pj = json.load(open(pmc))
-            except Exception:  # noqa: BLE001
-                pj = None
-        # ... the traffic of the dominant kernel from its own summary of the same passes
-        pd = None
-        pmc_dom = os.path.join(ROOT, "profiles", dom_pmc_file)
-        if pj is not None and os.path.exists(pmc_dom):
-            try:
-                pd = json.load(open(pmc_dom))
-            except Exception:  # noqa: BLE001
-                pd = None
-        # imported counters are flagged when they were not collected with the library this run loads
-        # (by the hash of the kernel sources, which survives a rebuild; the binary's hash rides along)
-        try:
-            import glob
-            import hashlib
-            lib_now = hashlib.sha256(open(_exp_env("GIPUMA_HIP_LIB", None) or abi.LIB_PATH, "rb").read()).hexdigest()[:16]
-            src_now = hashlib.sha256(b"".join(open(f, "rb").read() for f in sorted(
-                glob.glob(os.path.join(ROOT, "gipuma_amd", "csrc", "*.h*"))))).hexdigest()[:16]
-        except Exception:  # noqa: BLE001
-            lib_now = src_now = None
-
-        def stale(j):
-            return None if not j else (j.get("_src_sha16") != src_now)
-        # the imported traffic figure is only printed when it belongs to this build and this kernel time: counters
-        # collected from other kernel sources, or at a launch duration more than 5 % away from the one measured in this
-        # run, are refused (traffic = null, the reason in traffic_source.refused)
-        traffic, traffic_refused = None, None
-        if pd and "hbm_read_bytes_per_launch_x2corr" in pd:
-            ms_pmc = pd.get("_kernel_ms_profiled_mean")
-            if stale(pd):
-                traffic_refused = "collected with other kernel sources (src sha16 %s, this run %s)" % (pd.get("_src_sha16"), src_now)
-            elif ms_pmc and abs(ms_pmc - ms_launch) > 0.05 * ms_launch:
-                traffic_refused = "collected at %.3f ms per launch, this run measures %.3f ms (> 5 %% apart)" % (ms_pmc, ms_launch)
-            else:
-                traffic = (pd["hbm_read_bytes_per_launch_x2corr"] + pd["hbm_write_bytes_per_launch"]) / 1e9
-        imported_dom = {"measured_in_this_run": False, "file": "profiles/" + dom_pmc_file,
-                        "collected_at_kernel_ms": pd.get("_kernel_ms_profiled_mean") if pd else None,
-                        "collected_with_lib_sha16": pd.get("_lib_sha16") if pd else None, "commit": pd.get("_commit") if pd else None,
-                        "collected_with_src_sha16": pd.get("_src_sha16") if pd else None,
-                        "lib_sha16_of_this_run": lib_now, "src_sha16_of_this_run": src_now, "stale": stale(pd),
-                        "refused": traffic_refused, "note": pd.get("_note") if pd else None}
-        imported = {"measured_in_this_run": False, "file": "profiles/pmc_latest.json",
-                    "collected_at_kernel_ms": pj.get("_kernel_ms_profiled_mean") if pj else None,
-                    "collected_with_lib_sha16": pj.get("_lib_sha16") if pj else None, "commit": pj.get("_commit") if pj else None,
-                    "collected_with_src_sha16": pj.get("_src_sha16") if pj else None,
-                    "lib_sha16_of_this_run": lib_now, "src_sha16_of_this_run": src_now, "stale": stale(pj),
-                    "note": pj.get("_note") if pj else None}
         box = gs.params.box_hsize
-        S = ((box - 1) // 2 + 1) ** 2
-        r_ref = 0
-        dz = gs.params.max_disparity / 2.0
-        while dz >= 0.01:
-            r_ref += 1
-            dz /= 10.0
-        samples_per_frame = n_pix * (1 + iterations * (8 + r_ref)) * n_views * S
-        cols_l = int(sched["cols_launches"])
-        n_launch = 2 * iterations
-        # leading half-sweeps whose propagation costs are pushed by pm::push_kernel (pm_push.h: boxes 11 / 15 / 25, gray, best-N <= 4)
-        push_l = int(hs_pushed)  # (what the library reports for the timed solve: gipuma_hip_launch_times)
-        push_l = max(0, min(push_l, n_launch))
         out = {
             "metric": "Mpixels/sec/GPU (1600x1200, 10 src views, 8 iters)"
                       if args.config == "C" and not args.colour and args.scene == "smooth"
@@ -528,70 +459,177 @@ def main():
                        "device_ms_total": float(np.mean(total_ms)),
                        "device_ms_init": float(np.mean(init_ms))},
             "ranks": [dict(i, value=p["value"]) for i, p in zip(ident, per_rank)],
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_unit": "GB per launch (L2<->fabric incl. Infinity Cache hits)",
-                         "traffic_source": imported_dom,
-                         "kernel": ("pm::group_kernel: the propagation costs (close + far) of a half-sweep, one evaluation "
-                                    "per PLANE instead of per (pixel, plane); %d of the %d half-sweeps of a view are this "
-                                    "launch + one fused pm::sweep_kernel launch (accept replay + refinement); the %d before "
-                                    "them: pm::sweep_cols_kernel x%d and pm::push_kernel x%d"
-                                    % (int((gm[0] > 0).sum()), n_launch, first_plain, min(cols_l, n_launch), push_l))
-                                   if dom_is_group else
-                                   ("pm::sweep_group_kernel: one fused launch per half-sweep (one colour: close+far+refine; the "
-                                    "propagation costs evaluated once per PLANE, pm_group.h), %d of the %d half-sweeps of a view "
-                                    "(the %d before them: pm::sweep_cols_kernel x%d, and pm::push_kernel x%d, which evaluates "
-                                    "the propagation costs of the first %d half-sweeps once per plane)"
-                                    % (n_launch - first_plain, n_launch, first_plain, min(cols_l, n_launch), push_l, push_l))
-                                   if dom_is_fused else
-                                   ("pm::sweep_kernel: one fused launch per half-sweep (one colour: close+far+refine), "
-                                    "%d of the %d half-sweeps of a view (the %d before them: pm::sweep_cols_kernel x%d, "
-                                    "and pm::push_kernel x%d, which evaluates the propagation costs of the first %d "
-                                    "half-sweeps once per plane)"
-                                    % (n_launch - first_plain, n_launch, first_plain, min(cols_l, n_launch), push_l, push_l)),
-                         "kernel_ms": ms_launch,
-                         "kernel_ms_source": ("its own pair of HIP events on the library's stream (gipuma_hip_group_times), "
-                                              "mean over the kernel's launches, this run") if dom_is_group else
-                                             ("HIP events around each half-sweep on the library's stream "
-                                              "(gipuma_hip_launch_times), mean over the kernel's launches, this run"),
-                         "half_sweep_ms_mean_all": ms_half_sweep,
-                         "half_sweep_ms": [float(x) for x in hs.mean(axis=0)] if hs.size else None,
-                         "algorithmic_bytes_per_launch": alg,
-                         "second_kernel": ({"kernel": "pm::sweep_kernel (accept replay + refinement of the same half-sweeps)",
-                                            "kernel_ms": ms_sweep_launch, "algorithmic_bytes_per_launch": alg_sweep,
-                                            "achieved": alg_sweep / (ms_sweep_launch * 1e-3) / 1e9, "unit": "GB/s"}
-                                           if dom_is_group else None),
-                         "half_sweep_pair": ({"algorithmic_bytes": alg_half_sweep, "ms": ms_pair,
-                                              "achieved": alg_half_sweep / (ms_pair * 1e-3) / 1e9, "unit": "GB/s",
-                                              "what": "SURVEY 8d's figure for the three reference kernels a half-sweep "
-                                                      "replaces over the time of both launches"} if dom_is_group else None),
-                         "group_kernel_ms": [float(x) for x in gm.mean(axis=0)] if gm.size else None,
-                         "note": "compute/gather bound by construction (SURVEY F5): "
-                                 "%.3g patch samples/s" % (samples_per_frame / (np.mean(total_ms) * 1e-3))},
-            "quality": quality,
             "schedule": sched,
         }
-        # The roof that actually binds: vector-ALU issue.  SQ_INSTS_VALU comes from
-        # the committed PMC pass (see `source`), only the launch time is this run's.
-        if pj and "SQ_INSTS_VALU" in pj:
-            lane_ops = pj["SQ_INSTS_VALU"] * 64.0
-            peak = 256 * 4 * 32 * 2.4e9
-            out["roofline_valu"] = {
-                "bound": "valu", "achieved": lane_ops / (ms_half_sweep * 1e-3) / 1e12, "peak": peak / 1e12,
-                "unit": "T lane-instr/s", "frac": lane_ops / (ms_half_sweep * 1e-3) / peak,
-                "per": "half-sweep of a view (all its kernels: sums over the dispatches / %d)" % n_launch,
-                "valu_instr_per_window_load": pj["SQ_INSTS_VALU"] / max(1.0, pj.get("SQ_INSTS_VMEM_RD", 0.0)),
-                "source": dict(imported, counter="rocprofv3 --pmc SQ_INSTS_VALU")}
-        # ... and for the dominant kernel alone (its own summary of the same passes, this run's launch time)
-        if pd and "SQ_INSTS_VALU" in pd:
-            lane_ops = pd["SQ_INSTS_VALU"] * 64.0
-            peak = 256 * 4 * 32 * 2.4e9
-            out["roofline_valu_kernel"] = {
-                "bound": "valu", "kernel": dom_name, "achieved": lane_ops / (ms_launch * 1e-3) / 1e12,
-                "peak": peak / 1e12, "unit": "T lane-instr/s", "frac": lane_ops / (ms_launch * 1e-3) / peak,
-                "valu_wave_instr_per_launch": pd["SQ_INSTS_VALU"], "kernel_ms": ms_launch,
-                "source": dict(imported_dom, counter="rocprofv3 --pmc SQ_INSTS_VALU")}
-        if world == 1 and not args.no_extras:
+        if args.full:
+            ms_half_sweep = float(np.mean(sweep_ms))
+            alg = algorithmic_bytes_per_sweep_launch(n_pix, n_views)
+            # The dominant kernel: the fused pixel-per-lane sweep kernel.  Every half-sweep after the
+            # column-per-lane / pushed ones is exactly one launch of it, timed by its own pair of HIP events on
+            # the library's stream (gipuma_hip_launch_times); the earlier half-sweeps (other kernels, push
+            # launches) only enter the per-view mean reported beside it.
+            hs = np.asarray(half_sweeps, dtype=np.float64)  # [steps][2 * iterations]
+            first_plain = 0
+            if hs.size:
+                cols_first = int(sched["cols_launches"])
+                first_plain = min(hs.shape[1], max(cols_first, hs_pushed))
+                if sched["group_from"] >= 0:  # the dominant kernel's half-sweeps: those of the plane-keyed propagation
+                    first_plain = min(hs.shape[1], max(first_plain, sched["group_from"]))
+            dominant = hs[:, first_plain:] if hs.size and first_plain < hs.shape[1] else None
+            ms_launch = float(dominant.mean()) if dominant is not None else ms_half_sweep
+            # Where the propagation costs of a half-sweep come from pm::group_kernel (pm_group.h: box 15 on frames of
+            # >= 1024 tiles, from the fifth half-sweep on), a half-sweep is TWO launches -- that kernel (the cost
+            # evaluations of the reference's close + far kernels) and the fused sweep launch (their accept tests replayed
+            # + the refinement kernel) -- and the former is the dominant kernel by time.  It is timed by its own pair of
+            # HIP events on the library's stream (gipuma_hip_group_times); its algorithmic bytes are the close + far
+            # share of SURVEY 8d's per-launch figure: (28 + 28) B of state and 2 x 4 (N + 1) B of images per active pixel.
+            gm = np.asarray(group_ms, dtype=np.float64) if group_ms and len(group_ms[0]) else np.zeros((0, 0))
+            dom_is_group = bool(gm.size and (gm > 0).any())
+            dom_name, dom_pmc_file = "pm::sweep_kernel", "pmc_latest_sweep_kernel.json"
+            dom_is_fused = bool(sched["group_from"] >= 0 and sched["group_fused"])
+            if dom_is_fused:  # one launch per half-sweep: propagation per plane + accept replay + refinement
+                dom_name, dom_pmc_file = "pm::sweep_group_kernel", "pmc_latest_sweep_group_kernel.json"
+            ms_sweep_launch = ms_launch
+            if dom_is_group:
+                used = gm > 0
+                ms_group_launch = float(gm[used].mean())
+                ms_sweep_launch = float((hs - gm)[used].mean())  # the fused sweep launch of the same half-sweeps
+                alg_half_sweep, ms_pair = alg, ms_launch
+                alg = n_pix * (56 + 8 * (n_views + 1)) / 2.0
+                alg_sweep = n_pix * (20 + 4 * (n_views + 1)) / 2.0
+                ms_launch = ms_group_launch
+                dom_name, dom_pmc_file = "pm::group_kernel", "pmc_latest_group_kernel.json"
+            achieved = alg / (ms_launch * 1e-3) / 1e9
+            # HBM-side bytes per sweep launch and VALU instruction counts are NOT measured in this run: they
+            # come from the PMC passes of the same command (scripts/pmc_passes.sh -> profiles/pmc_latest.json),
+            # FETCH_SIZE x2 (gfx950 correction, MI355X_MICROARCH.md HBM section) + WRITE_SIZE, separate --pmc
+            # passes; the object says so
+            pj = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
+            if os.path.exists(pmc) and args.config == "C" and args.scene == "smooth" and not args.colour:
+                try:
+                    pj = json.load(open(pmc))
+                except Exception:  # noqa: BLE001
+                    pj = None
+            # ... the traffic of the dominant kernel from its own summary of the same passes
+            pd = None
+            pmc_dom = os.path.join(ROOT, "profiles", dom_pmc_file)
+            if pj is not None and os.path.exists(pmc_dom):
+                try:
+                    pd = json.load(open(pmc_dom))
+                except Exception:  # noqa: BLE001
+                    pd = None
+            # imported counters are flagged when they were not collected with the library this run loads
+            # (by the hash of the kernel sources, which survives a rebuild; the binary's hash rides along)
+            try:
+                import glob
+                import hashlib
+                lib_now = hashlib.sha256(open(_exp_env("GIPUMA_HIP_LIB", None) or abi.LIB_PATH, "rb").read()).hexdigest()[:16]
+                src_now = hashlib.sha256(b"".join(open(f, "rb").read() for f in sorted(
+                    glob.glob(os.path.join(ROOT, "gipuma_amd", "csrc", "*.h*"))))).hexdigest()[:16]
+            except Exception:  # noqa: BLE001
+                lib_now = src_now = None
+
+            def stale(j):
+                return None if not j else (j.get("_src_sha16") != src_now)
+            # the imported traffic figure is only printed when it belongs to this build and this kernel time: counters
+            # collected from other kernel sources, or at a launch duration more than 5 % away from the one measured in this
+            # run, are refused (traffic = null, the reason in traffic_source.refused)
+            traffic, traffic_refused = None, None
+            if pd and "hbm_read_bytes_per_launch_x2corr" in pd:
+                ms_pmc = pd.get("_kernel_ms_profiled_mean")
+                if stale(pd):
+                    traffic_refused = "collected with other kernel sources (src sha16 %s, this run %s)" % (pd.get("_src_sha16"), src_now)
+                elif ms_pmc and abs(ms_pmc - ms_launch) > 0.05 * ms_launch:
+                    traffic_refused = "collected at %.3f ms per launch, this run measures %.3f ms (> 5 %% apart)" % (ms_pmc, ms_launch)
+                else:
+                    traffic = (pd["hbm_read_bytes_per_launch_x2corr"] + pd["hbm_write_bytes_per_launch"]) / 1e9
+            imported_dom = {"measured_in_this_run": False, "file": "profiles/" + dom_pmc_file,
+                            "collected_at_kernel_ms": pd.get("_kernel_ms_profiled_mean") if pd else None,
+                            "collected_with_lib_sha16": pd.get("_lib_sha16") if pd else None, "commit": pd.get("_commit") if pd else None,
+                            "collected_with_src_sha16": pd.get("_src_sha16") if pd else None,
+                            "lib_sha16_of_this_run": lib_now, "src_sha16_of_this_run": src_now, "stale": stale(pd),
+                            "refused": traffic_refused, "note": pd.get("_note") if pd else None}
+            imported = {"measured_in_this_run": False, "file": "profiles/pmc_latest.json",
+                        "collected_at_kernel_ms": pj.get("_kernel_ms_profiled_mean") if pj else None,
+                        "collected_with_lib_sha16": pj.get("_lib_sha16") if pj else None, "commit": pj.get("_commit") if pj else None,
+                        "collected_with_src_sha16": pj.get("_src_sha16") if pj else None,
+                        "lib_sha16_of_this_run": lib_now, "src_sha16_of_this_run": src_now, "stale": stale(pj),
+                        "note": pj.get("_note") if pj else None}
+            S = ((box - 1) // 2 + 1) ** 2
+            r_ref = 0
+            dz = gs.params.max_disparity / 2.0
+            while dz >= 0.01:
+                r_ref += 1
+                dz /= 10.0
+            samples_per_frame = n_pix * (1 + iterations * (8 + r_ref)) * n_views * S
+            cols_l = int(sched["cols_launches"])
+            n_launch = 2 * iterations
+            # leading half-sweeps whose propagation costs are pushed by pm::push_kernel (pm_push.h: boxes 11 / 15 / 25, gray, best-N <= 4)
+            push_l = int(hs_pushed)  # (what the library reports for the timed solve: gipuma_hip_launch_times)
+            push_l = max(0, min(push_l, n_launch))
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "traffic_unit": "GB per launch (L2<->fabric incl. Infinity Cache hits)",
+                               "traffic_source": imported_dom,
+                               "kernel": ("pm::group_kernel: the propagation costs (close + far) of a half-sweep, one evaluation "
+                                          "per PLANE instead of per (pixel, plane); %d of the %d half-sweeps of a view are this "
+                                          "launch + one fused pm::sweep_kernel launch (accept replay + refinement); the %d before "
+                                          "them: pm::sweep_cols_kernel x%d and pm::push_kernel x%d"
+                                          % (int((gm[0] > 0).sum()), n_launch, first_plain, min(cols_l, n_launch), push_l))
+                                         if dom_is_group else
+                                         ("pm::sweep_group_kernel: one fused launch per half-sweep (one colour: close+far+refine; the "
+                                          "propagation costs evaluated once per PLANE, pm_group.h), %d of the %d half-sweeps of a view "
+                                          "(the %d before them: pm::sweep_cols_kernel x%d, and pm::push_kernel x%d, which evaluates "
+                                          "the propagation costs of the first %d half-sweeps once per plane)"
+                                          % (n_launch - first_plain, n_launch, first_plain, min(cols_l, n_launch), push_l, push_l))
+                                         if dom_is_fused else
+                                         ("pm::sweep_kernel: one fused launch per half-sweep (one colour: close+far+refine), "
+                                          "%d of the %d half-sweeps of a view (the %d before them: pm::sweep_cols_kernel x%d, "
+                                          "and pm::push_kernel x%d, which evaluates the propagation costs of the first %d "
+                                          "half-sweeps once per plane)"
+                                          % (n_launch - first_plain, n_launch, first_plain, min(cols_l, n_launch), push_l, push_l)),
+                               "kernel_ms": ms_launch,
+                               "kernel_ms_source": ("its own pair of HIP events on the library's stream (gipuma_hip_group_times), "
+                                                    "mean over the kernel's launches, this run") if dom_is_group else
+                                                   ("HIP events around each half-sweep on the library's stream "
+                                                    "(gipuma_hip_launch_times), mean over the kernel's launches, this run"),
+                               "half_sweep_ms_mean_all": ms_half_sweep,
+                               "half_sweep_ms": [float(x) for x in hs.mean(axis=0)] if hs.size else None,
+                               "algorithmic_bytes_per_launch": alg,
+                               "second_kernel": ({"kernel": "pm::sweep_kernel (accept replay + refinement of the same half-sweeps)",
+                                                  "kernel_ms": ms_sweep_launch, "algorithmic_bytes_per_launch": alg_sweep,
+                                                  "achieved": alg_sweep / (ms_sweep_launch * 1e-3) / 1e9, "unit": "GB/s"}
+                                                 if dom_is_group else None),
+                               "half_sweep_pair": ({"algorithmic_bytes": alg_half_sweep, "ms": ms_pair,
+                                                    "achieved": alg_half_sweep / (ms_pair * 1e-3) / 1e9, "unit": "GB/s",
+                                                    "what": "SURVEY 8d's figure for the three reference kernels a half-sweep "
+                                                            "replaces over the time of both launches"} if dom_is_group else None),
+                               "group_kernel_ms": [float(x) for x in gm.mean(axis=0)] if gm.size else None,
+                               "note": "compute/gather bound by construction (SURVEY F5): "
+                                       "%.3g patch samples/s" % (samples_per_frame / (np.mean(total_ms) * 1e-3))}
+            out["quality"] = quality
+            # The roof that actually binds: vector-ALU issue.  SQ_INSTS_VALU comes from
+            # the committed PMC pass (see `source`), only the launch time is this run's.
+            if pj and "SQ_INSTS_VALU" in pj:
+                lane_ops = pj["SQ_INSTS_VALU"] * 64.0
+                peak = 256 * 4 * 32 * 2.4e9
+                out["roofline_valu"] = {
+                    "bound": "valu", "achieved": lane_ops / (ms_half_sweep * 1e-3) / 1e12, "peak": peak / 1e12,
+                    "unit": "T lane-instr/s", "frac": lane_ops / (ms_half_sweep * 1e-3) / peak,
+                    "per": "half-sweep of a view (all its kernels: sums over the dispatches / %d)" % n_launch,
+                    "valu_instr_per_window_load": pj["SQ_INSTS_VALU"] / max(1.0, pj.get("SQ_INSTS_VMEM_RD", 0.0)),
+                    "source": dict(imported, counter="rocprofv3 --pmc SQ_INSTS_VALU")}
+            # ... and for the dominant kernel alone (its own summary of the same passes, this run's launch time)
+            if pd and "SQ_INSTS_VALU" in pd:
+                lane_ops = pd["SQ_INSTS_VALU"] * 64.0
+                peak = 256 * 4 * 32 * 2.4e9
+                out["roofline_valu_kernel"] = {
+                    "bound": "valu", "kernel": dom_name, "achieved": lane_ops / (ms_launch * 1e-3) / 1e12,
+                    "peak": peak / 1e12, "unit": "T lane-instr/s", "frac": lane_ops / (ms_launch * 1e-3) / peak,
+                    "valu_wave_instr_per_launch": pd["SQ_INSTS_VALU"], "kernel_ms": ms_launch,
+                    "source": dict(imported_dom, counter="rocprofv3 --pmc SQ_INSTS_VALU")}
+        if world == 1 and args.full and not args.no_extras:
             from gipuma_amd.problem import GlobalState, runcuda
             # (a) the same workload with every exact work-reduction switched off (skip rules A/D/H, early
             #     termination): what a scene that defeats them would cost
@@ -778,7 +816,7 @@ def main():
                 out["value_other_configs"] = dict(others_out, what="BASELINE.json configs A, B, D, and config C's frame with the "
                                                   "reference's default window (box 19) / with -color_processing (T = float4); "
                                                   "one reference view at a time, default mode, best of two solves")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             import tempfile
             from gipuma_amd.problem import save_problem
             with tempfile.TemporaryDirectory() as td:  # the same frames, copied back from HBM

@@ -165,7 +165,7 @@ def test_bench_two_ranks_on_hardware(hip):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--steps", "1",
-                        "--warmup", "0", "--config", "B", "--no-extras", "--no-cpu-baseline"],
+                        "--warmup", "0", "--config", "B", "--full", "--no-extras", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
