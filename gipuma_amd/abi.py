@@ -71,6 +71,27 @@ class Timing(C.Structure):
     ]
 
 
+FUSION_MAX_VIEWS = 512  # GIPUMA_HIP_FUSION_MAX_VIEWS (MAX_IMAGES, config.h:2)
+
+
+class FusionView(C.Structure):
+    """gipuma_hip_fusion_view: one view's device planes and float32 camera constants (gipuma_amd.fusion.view_constants)"""
+    _fields_ = [
+        ("norm4", C.c_void_p), ("gray", C.c_void_p), ("bp", C.c_float * 9), ("c", C.c_float * 3),
+        ("P", C.c_float * 12), ("fb", C.c_float),
+    ]
+
+
+class FusionDesc(C.Structure):
+    """gipuma_hip_fusion_desc: views, size and the fusion parameters (--disp_thresh, --normal_thresh, --num_consistent)"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("rows", C.c_int32), ("cols", C.c_int32), ("n_views", C.c_int32),
+        ("views", C.POINTER(FusionView)), ("disp_thresh", C.c_float), ("normal_thresh", C.c_float),
+        ("num_consistent", C.c_int32), ("depth_min", C.c_float), ("depth_max", C.c_float),
+        ("device_id", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
 # every symbol include/gipuma_hip.h declares: (name, restype, argtypes)
 _FP = C.POINTER(C.c_float)
 SYMBOLS = [
@@ -94,6 +115,11 @@ SYMBOLS = [
     ("gipuma_hip_group_times", C.c_int, [C.c_void_p, _FP, C.c_int, C.POINTER(C.c_int)]),
     ("gipuma_hip_schedule", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("gipuma_hip_run", C.c_int, [C.POINTER(Desc), _FP, _FP, C.POINTER(Timing)]),
+    ("gipuma_hip_fuse", C.c_int, [C.POINTER(FusionDesc), C.POINTER(C.c_void_p)]),
+    ("gipuma_hip_fusion_count", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _FP]),
+    ("gipuma_hip_fusion_points", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
+    ("gipuma_hip_fusion_used", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("gipuma_hip_fusion_free", C.c_int, [C.c_void_p]),
 ]
 
 _lib = None

@@ -17,7 +17,11 @@ MI355X-first differences from the shell loop:
     another (bench.py `value_views_in_flight`: +2 % with 2 / 3 views on config C since the fused launches of
     round 4 -- they leave little to overlap --, far more on frames whose tiles do not fill the GPU, e.g. config B);
   * results land in <output>/<refname>/{disp.dmb, normals.dmb, cost.dmb} -- the dumps the
-    reference writes (main.cpp:1001-1015) and fusibile reads.
+    reference writes (main.cpp:1001-1015) and the depth-map fusion reads (gipuma_amd.fusion);
+  * --fuse: the results of this run are also fused on the GPU, from memory, into <output>/fused.ply (with
+    --disp_thresh / --normal_thresh / --num_consistent and the depth range) -- what the reference's
+    scripts leave to an external CUDA tool after the loop (scripts/dtu_fast.sh:56-57).  One process only: with
+    WORLD_SIZE > 1 run `python -m gipuma_amd.fusion` on the output folder instead.
 
 Images: what the reference's scripts hand to imread (main.cpp:739-751) -- PNG, JPG (through PIL), binary PGM / PPM.
 Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
@@ -133,10 +137,19 @@ def main(argv=None):
                     help="exact: bit-identical to the numerical model (default); fast: tolerance-judged kernels "
                          "(GIPUMA_HIP_FLAG_FAST); literal: the reference's own operation order, bit-identical to the "
                          "reference's code, about 20x slower (GIPUMA_HIP_FLAG_LITERAL)")
+    pa.add_argument("--fuse", action="store_true",
+                    help="fuse the views solved in this run into <output-folder>/fused.ply (gipuma_amd.fusion)")
+    pa.add_argument("--disp_thresh", type=float, default=0.1, help="with --fuse")
+    pa.add_argument("--normal_thresh", type=float, default=30.0, help="with --fuse, degrees")
+    pa.add_argument("--num_consistent", type=int, default=3, help="with --fuse")
     args = pa.parse_args(argv)
     # the reference parses these with sscanf("%f") into float fields (main.cpp:300-360)
-    for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale"):
+    for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
+              "normal_thresh"):
         setattr(args, k, float(np.float32(getattr(args, k))))
+    if args.fuse and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--fuse works within one process (there is no exchange of results between ranks): run "
+                         "`python -m gipuma_amd.fusion --input-folder %s ...` once every rank is done" % args.output_folder)
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -169,6 +182,7 @@ def main(argv=None):
     report = []
     in_flight = max(1, args.in_flight)
     pending = collections.deque()  # (session, reference name, source names, start time, timing or None)
+    solved = {}  # reference name -> norm4 (host), for --fuse
 
     def retire():
         s, ref_name, sources, tw0, t = pending.popleft()
@@ -182,6 +196,8 @@ def main(argv=None):
         dmb.write_dmb(os.path.join(folder, "disp.dmb"), n4[..., 3])
         dmb.write_dmb(os.path.join(folder, "normals.dmb"), n4[..., :3])
         dmb.write_dmb(os.path.join(folder, "cost.dmb"), cost)
+        if args.fuse:
+            solved[ref_name] = n4
         entry = {"ref": ref_name, "sources": sources, "wall_ms": wall_ms,
                  "mpix_per_s_wall": rows * cols / (wall_ms * 1e-3) / 1e6}
         if t is not None:  # one view at a time: the device time is that view's alone
@@ -226,12 +242,29 @@ def main(argv=None):
         # torch hands out again once they are freed (the library refuses while a session still uses them)
         abi.load_library().gipuma_hip_cache_clear()
     t_batch = time.perf_counter() - t_batch0
+    fused = None
+    if args.fuse:
+        # the views solved here, in the scan's order (that of the fusion CLI on the dumps); skipped ones are left out
+        order = [n for n in names if n in solved]
+        if len(order) < 2:
+            raise SystemExit("--fuse needs at least 2 solved views, this run solved %d" % len(order))
+        from . import fusion
+        points, info = fusion.fuse([solved[n] for n in order], [dev[names.index(n)] for n in order],
+                                   [P_all[names.index(n)] for n in order], args.cam_scale, args.disp_thresh,
+                                   args.normal_thresh, args.num_consistent, args.depth_min, args.depth_max,
+                                   device_id=dev_index, return_info=True)
+        dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
+        fused = {"points": int(len(points)), "device_ms": info["device_ms"],
+                 "views": [{"name": n, "emitted": int(c)} for n, c in zip(order, info["per_view"])]}
     with open(os.path.join(args.output_folder, "batch_rank%d.json" % rank), "w") as f:
         n_done = sum(1 for r in report if "skipped" not in r)
-        json.dump({"rank": rank, "world": world, "device": dev_index, "load_seconds": t_load,
-                   "in_flight": in_flight, "batch_seconds": t_batch,
-                   "mpix_per_s_batch": n_done * rows * cols / max(t_batch, 1e-9) / 1e6,
-                   "views": report}, f, indent=1)
+        out = {"rank": rank, "world": world, "device": dev_index, "load_seconds": t_load,
+               "in_flight": in_flight, "batch_seconds": t_batch,
+               "mpix_per_s_batch": n_done * rows * cols / max(t_batch, 1e-9) / 1e6,
+               "views": report}
+        if fused is not None:
+            out["fusion"] = fused
+        json.dump(out, f, indent=1)
     print("rank %d/%d: %d reference views on cuda:%d" % (rank, world, len(report), dev_index))
     return 0
 

@@ -526,6 +526,11 @@ int gipuma_hip_version(void) { return GIPUMA_HIP_ABI_VERSION; }
 
 const char *gipuma_hip_last_error(void) { return g_err.c_str(); }
 
+#ifndef GIPUMA_HIP_FLAVOUR_TU
+// failures of the fusion entry points (gipuma_fuse.hip) become this thread's last error too; hidden, not part of the C-ABI
+__attribute__((visibility("hidden"))) void gipuma_set_last_error(const char *text) { g_err = text; }
+#endif
+
 int gipuma_hip_device_count(void)
 {
     int n = 0;

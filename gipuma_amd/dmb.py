@@ -1,6 +1,7 @@
 """The reference's `.dmb` dumps (fileIoUtils.h:247-368): int32 {type=1, h, w, nb} followed by
 h*w*nb float32, row-major.  `disp.dmb` holds norm4.w (depth), `normals.dmb` the world normals
-(main.cpp:1001-1015); these are the "CPU-readable dumps" external tools such as fusibile read."""
+(main.cpp:1001-1015); these are the "CPU-readable dumps" the depth-map fusion reads (gipuma_amd.fusion, the in-tree
+consumer in place of the external fusibile tool of the reference's scripts)."""
 import numpy as np
 
 
@@ -65,6 +66,15 @@ def write_ply_binary(path, depth, normals, gray, M_inv, P_col34):
     v["red"] = v["green"] = v["blue"] = g
     with open(path, "wb") as f:
         f.write((_PLY_HEADER % (rows * cols)).encode())
+        v.tofile(f)
+
+
+def write_points_ply(path, points):
+    """a point cloud (structured array of _PLY_VERTEX, e.g. gipuma_amd.fusion.fuse's result) as a binary PLY with the
+    vertex layout of write_ply_binary"""
+    v = np.ascontiguousarray(points, dtype=_PLY_VERTEX)
+    with open(path, "wb") as f:
+        f.write((_PLY_HEADER % len(v)).encode())
         v.tofile(f)
 
 

@@ -235,6 +235,55 @@ int gipuma_hip_schedule(gipuma_hip_session *s, int info[4]);
 int gipuma_hip_run(const gipuma_hip_desc *desc, float *norm4_out, float *cost_out,
                    gipuma_hip_timing *timing);
 
+/* ---- depth-map fusion: per-view (n_world, depth) planes -> one point cloud ----
+ * The step the reference's scripts hand to an external tool after the per-view solves (scripts/dtu_fast.sh:23-26,
+ * --disp_thresh / --normal_thresh / --num_consistent).  No parity with that tool is claimed; the contract is
+ * DESIGN.md 11.  In short: views are taken in order i = 0..n_views-1; a pixel of view i with a valid depth that no
+ * earlier view has marked is back-projected to X = c_i + z (bp_i (x, y, 1)); every other view j projects X with P_j,
+ * rounds to the nearest pixel q and counts as consistent when q is inside, its depth z' is valid,
+ * |fb_j / h_2 - fb_j / z'| < disp_thresh and n . n' > cos(normal_thresh).  With at least num_consistent such views
+ * the mean of the points, the normalised sum of the normals and the rounded mean gray are emitted, and every
+ * consistent q is marked in its view.  Points come out in (view, y, x) order, bit for bit reproducible. */
+#define GIPUMA_HIP_FUSION_MAX_VIEWS 512 /* MAX_IMAGES, config.h:2 */
+
+/* One view: device planes and float32 constants derived on the host in double from the view's own (not re-centred)
+ * P = K [R | -R C], K scaled by cam_scale (gipuma_amd/fusion.py view_constants). */
+typedef struct gipuma_hip_fusion_view {
+    const float *norm4; /* device, rows*cols*4 floats (n_world.xyz, depth) as gipuma_hip_finalize leaves them */
+    const float *gray;  /* device, rows*cols floats 0..255, or NULL (gray 0) */
+    float bp[9];        /* R^T K^-1, row-major: world direction of pixel (x, y, 1) */
+    float c[3];         /* camera centre C */
+    float P[12];        /* [K R | -K R C], row-major 3x4 */
+    float fb;           /* f32(f32(K[0][0]) * 0.54f): focal length x baseline (cameraGeometryUtils.h:103-107, :305) */
+} gipuma_hip_fusion_view;
+
+typedef struct gipuma_hip_fusion_desc {
+    uint32_t abi_version;                /* GIPUMA_HIP_ABI_VERSION */
+    int32_t rows, cols;                  /* of every view */
+    int32_t n_views;                     /* 2 .. GIPUMA_HIP_FUSION_MAX_VIEWS */
+    const gipuma_hip_fusion_view *views; /* host array of n_views entries */
+    float disp_thresh;                   /* --disp_thresh, disparity units (pixels) */
+    float normal_thresh;                 /* --normal_thresh, degrees; cos_t = f32(cos(normal_thresh * pi / 180)) in double */
+    int32_t num_consistent;              /* --num_consistent, >= 1 */
+    float depth_min, depth_max;          /* depths outside are invalid; <= 0: no bound */
+    int32_t device_id;                   /* HIP device ordinal */
+    void *stream;                        /* hipStream_t to launch on, NULL = one the library creates for the call */
+} gipuma_hip_fusion_desc;
+
+typedef struct gipuma_hip_fusion gipuma_hip_fusion;
+
+/* Runs the fusion and returns a handle that holds the points in device memory; blocks until they are complete.  The
+ * planes must be complete when it is called (as for gipuma_hip_create). */
+int gipuma_hip_fuse(const gipuma_hip_fusion_desc *desc, gipuma_hip_fusion **out);
+/* total points, points emitted per view (n_views entries) and the device time of the fusion in ms (each may be NULL) */
+int gipuma_hip_fusion_count(const gipuma_hip_fusion *f, int64_t *n_points, int64_t *per_view, float *device_ms);
+/* points first .. first + count - 1 as binary PLY vertices of 27 bytes each: float x, y, z, nx, ny, nz (little
+ * endian) and the gray byte three times (the vertex of storePlyFileBinary, displayUtils.h:78-159) */
+int gipuma_hip_fusion_points(const gipuma_hip_fusion *f, void *vertices, int64_t first, int64_t count);
+/* the final `used` marks: n_views * rows * cols bytes (0 / 1), view-major */
+int gipuma_hip_fusion_used(const gipuma_hip_fusion *f, uint8_t *masks);
+int gipuma_hip_fusion_free(gipuma_hip_fusion *f);
+
 #ifdef __cplusplus
 }
 #endif
