@@ -115,6 +115,10 @@ SYMBOLS = [
     ("gipuma_hip_group_times", C.c_int, [C.c_void_p, _FP, C.c_int, C.POINTER(C.c_int)]),
     ("gipuma_hip_schedule", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("gipuma_hip_run", C.c_int, [C.POINTER(Desc), _FP, _FP, C.POINTER(Timing)]),
+    ("gipuma_hip_seed_planes", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    ("gipuma_hip_solve_seeded", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Timing)]),
+    ("gipuma_hip_downsample", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p]),
     ("gipuma_hip_fuse", C.c_int, [C.POINTER(FusionDesc), C.POINTER(C.c_void_p)]),
     ("gipuma_hip_fusion_count", C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _FP]),
     ("gipuma_hip_fusion_points", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),

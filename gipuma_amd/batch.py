@@ -18,6 +18,10 @@ MI355X-first differences from the shell loop:
     round 4 -- they leave little to overlap --, far more on frames whose tiles do not fill the GPU, e.g. config B);
   * results land in <output>/<refname>/{disp.dmb, normals.dmb, cost.dmb} -- the dumps the
     reference writes (main.cpp:1001-1015) and the depth-map fusion reads (gipuma_amd.fusion);
+  * --levels N (default 1: today's single-level solve): coarse-to-fine over an N-level pyramid of the scan (DESIGN.md 12,
+    gipuma_amd.pyramid) -- the coarse planes are made once per scan, every view solves its coarsest level plainly and
+    seeds each finer level from the one below; --level_iterations a,b,.. (coarsest first; default for --levels 2:
+    <iterations>,2).  Views are solved one at a time; with --in_flight 1 the report carries per-level device times;
   * --fuse: the results of this run are also fused on the GPU, from memory, into <output>/fused.ply (with
     --disp_thresh / --normal_thresh / --num_consistent and the depth range) -- what the reference's
     scripts leave to an external CUDA tool after the loop (scripts/dtu_fast.sh:56-57).  One process only: with
@@ -137,6 +141,10 @@ def main(argv=None):
                     help="exact: bit-identical to the numerical model (default); fast: tolerance-judged kernels "
                          "(GIPUMA_HIP_FLAG_FAST); literal: the reference's own operation order, bit-identical to the "
                          "reference's code, about 20x slower (GIPUMA_HIP_FLAG_LITERAL)")
+    pa.add_argument("--levels", type=int, default=1,
+                    help="pyramid levels of a coarse-to-fine solve (1: the plain solve; gipuma_amd.pyramid)")
+    pa.add_argument("--level_iterations", default="",
+                    help="with --levels > 1: iterations per level, coarsest first (default: <iterations>,2,..,2)")
     pa.add_argument("--fuse", action="store_true",
                     help="fuse the views solved in this run into <output-folder>/fused.ply (gipuma_amd.fusion)")
     pa.add_argument("--disp_thresh", type=float, default=0.1, help="with --fuse")
@@ -147,6 +155,12 @@ def main(argv=None):
     for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
               "normal_thresh"):
         setattr(args, k, float(np.float32(getattr(args, k))))
+    if args.levels < 1:
+        raise SystemExit("--levels must be >= 1")
+    level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
+        [args.iterations] + [2] * (args.levels - 1)
+    if args.levels > 1 and len(level_iterations) != args.levels:
+        raise SystemExit("--level_iterations needs %d values, coarsest first" % args.levels)
     if args.fuse and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--fuse works within one process (there is no exchange of results between ranks): run "
                          "`python -m gipuma_amd.fusion --input-folder %s ...` once every rank is done" % args.output_folder)
@@ -190,6 +204,9 @@ def main(argv=None):
             n4, cost = s.get_state()  # waits for the session's stream
         finally:
             s.close()
+        record(ref_name, sources, tw0, t, n4, cost)
+
+    def record(ref_name, sources, tw0, t, n4, cost, levels=None):
         wall_ms = (time.perf_counter() - tw0) * 1e3  # session set-up + solve (+ what ran beside it) + download
         folder = os.path.join(args.output_folder, os.path.splitext(ref_name)[0])
         os.makedirs(folder, exist_ok=True)
@@ -202,8 +219,15 @@ def main(argv=None):
                  "mpix_per_s_wall": rows * cols / (wall_ms * 1e-3) / 1e6}
         if t is not None:  # one view at a time: the device time is that view's alone
             entry.update({"device_ms": t.ms_total, "mpix_per_s": rows * cols / (t.ms_total * 1e-3) / 1e6})
+        if levels is not None:  # (--levels > 1, one view at a time: device times per level, coarsest first)
+            ms = sum(lv["ms_total"] for lv in levels)
+            entry.update({"levels": levels, "device_ms": ms, "mpix_per_s": rows * cols / (ms * 1e-3) / 1e6})
         report.append(entry)
 
+    pyr = None
+    if args.levels > 1:
+        from . import pyramid
+        pyr = pyramid.ScanPyramid(dev, args.levels)  # the coarse planes of the whole scan, once
     t_batch0 = time.perf_counter()
     try:
         for ref_name in mine:
@@ -211,6 +235,13 @@ def main(argv=None):
             cs, used, ap_view = plan_views(P_all, names, ref_idx, cols, rows, ap, args.cam_scale)
             if len(used) < 2:
                 report.append({"ref": ref_name, "skipped": "no source view inside the angle cone"})
+                continue
+            if pyr is not None:
+                # view selection and the depth range were decided above, on the finest level; every level reuses them
+                tw0 = time.perf_counter()
+                n4, cost, times = pyramid.solve_view(pyr, P_all, used, ap_view, level_iterations, seed=args.seed,
+                                                     mode=args.mode, cam_scale=args.cam_scale, timing=in_flight == 1)
+                record(ref_name, [names[i] for i in used[1:]], tw0, None, n4, cost, times if in_flight == 1 else None)
                 continue
             imgs = [dev[i] for i in used]
             # the scan's planes stay put for the whole batch: what the library derives from them (8-bit
@@ -238,6 +269,8 @@ def main(argv=None):
         for leftover in pending:
             leftover[0].close()
         pending.clear()
+        if pyr is not None:
+            pyr.close()  # (clears the image cache before the coarse planes are released)
         # ... nor the image cache: its entries are keyed by the device addresses of `dev`'s tensors, which
         # torch hands out again once they are freed (the library refuses while a session still uses them)
         abi.load_library().gipuma_hip_cache_clear()
@@ -260,6 +293,8 @@ def main(argv=None):
         n_done = sum(1 for r in report if "skipped" not in r)
         out = {"rank": rank, "world": world, "device": dev_index, "load_seconds": t_load,
                "in_flight": in_flight, "batch_seconds": t_batch,
+               **({"levels": args.levels, "level_iterations": level_iterations, "pyramid_device_ms": pyr.device_ms}
+                  if pyr is not None else {}),
                "mpix_per_s_batch": n_done * rows * cols / max(t_batch, 1e-9) / 1e6,
                "views": report}
         if fused is not None:

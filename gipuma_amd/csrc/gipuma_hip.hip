@@ -61,7 +61,9 @@ extern "C" {
     int P##solve(void *s, gipuma_hip_timing *timing);                                                                   \
     int P##launch_times(void *s, float *ms_half_sweep, int capacity, int *n_half_sweeps, int *n_pushed);                \
     int P##group_times(void *s, float *ms_group, int capacity, int *n_half_sweeps);                                     \
-    int P##schedule(void *s, int info[4]);
+    int P##schedule(void *s, int info[4]);                                                                              \
+    int P##seed_planes(void *s, const float *prior_dev, int prior_rows, int prior_cols, int shift);                     \
+    int P##solve_seeded(void *s, const float *prior_dev, int prior_rows, int prior_cols, int shift, gipuma_hip_timing *timing);
 DECLARE_FLAVOUR(gipuma_hipf_)
 DECLARE_FLAVOUR(gipuma_hipl_)
 #undef DECLARE_FLAVOUR
@@ -83,10 +85,13 @@ struct FlavourApi {
     int (*launch_times)(void *, float *, int, int *, int *);
     int (*group_times)(void *, float *, int, int *);
     int (*schedule)(void *, int *);
+    int (*seed_planes)(void *, const float *, int, int, int);
+    int (*solve_seeded)(void *, const float *, int, int, int, gipuma_hip_timing *);
 };
 #define FLAVOUR_API(P)                                                                                                  \
     {P##last_error, P##cache_clear, P##create, P##destroy, P##init_planes, P##sweep, P##finalize, P##eval_cost,        \
-     P##get_state, P##set_state, P##state_device_ptrs, P##solve, P##launch_times, P##group_times, P##schedule}
+     P##get_state, P##set_state, P##state_device_ptrs, P##solve, P##launch_times, P##group_times, P##schedule,         \
+     P##seed_planes, P##solve_seeded}
 static const FlavourApi kFastApi = FLAVOUR_API(gipuma_hipf_), kLiteralApi = FLAVOUR_API(gipuma_hipl_);
 #undef FLAVOUR_API
 #else
@@ -516,6 +521,29 @@ int launch_dense(gipuma_hip_session *s, bool generate, float4 *planes, float *co
     hipLaunchKernelGGL(k.fn, dim3(s->gx * gy), dim3(pm::kThreads), k.lds, s->stream, s->dp, planes, cost_out, s->tune);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+// What gipuma_hip_init_planes and gipuma_hip_seed_planes share: the launches in front of the kernel that writes a new plane
+// field, and the session's state once that field and its costs are enqueued.
+int new_planes_reset(gipuma_hip_session *s)
+{
+    // (a fresh solve starts with fresh hints, so that repeated solves of a session do the same work)
+    HIP_OK(hipMemsetAsync(s->et_hint, 0, s->et_hint_bytes, s->stream));
+    HIP_OK(hipMemsetAsync(s->et_stat, 0, 3 * pm::kEtSlot * sizeof(unsigned), s->stream));
+    s->worder_valid = false;  // (listed again by the first sweep: part of every solve)
+    if (s->tile_clock) {  // (no durations yet: the first fused launch of either colour runs in the plain order)
+        HIP_OK(hipMemsetAsync(s->tile_clock, 0, 4 * (size_t)s->tiles * sizeof(unsigned long long), s->stream));
+    }
+    if (s->seen_pos) HIP_OK(hipMemsetAsync(s->seen_pos, 0, (size_t)s->rows * s->cols, s->stream));  // rule (S): new planes
+    return 0;
+}
+
+void new_planes_installed(gipuma_hip_session *s, int rc)
+{
+    if (!rc) s->costs_trusted = true;
+    s->finalized = false;
+    s->prev1 = s->prev2 = -1;
+    s->push_valid = -1;
 }
 
 }  // namespace
@@ -1114,19 +1142,31 @@ int gipuma_hip_init_planes(gipuma_hip_session *s)
     FORWARD(s, init_planes);
     if (!s) return fail(GIPUMA_HIP_ERR_ARG, "null session");
     HIP_OK(hipSetDevice(s->device));
-    // (a fresh solve starts with fresh hints, so that repeated solves of a session do the same work)
-    HIP_OK(hipMemsetAsync(s->et_hint, 0, s->et_hint_bytes, s->stream));
-    HIP_OK(hipMemsetAsync(s->et_stat, 0, 3 * pm::kEtSlot * sizeof(unsigned), s->stream));
-    s->worder_valid = false;  // (listed again by the first sweep: part of every solve)
-    if (s->tile_clock) {  // (no durations yet: the first fused launch of either colour runs in the plain order)
-        HIP_OK(hipMemsetAsync(s->tile_clock, 0, 4 * (size_t)s->tiles * sizeof(unsigned long long), s->stream));
+    int rc = new_planes_reset(s);
+    if (!rc) rc = launch_dense(s, true, s->norm4, s->cost);
+    new_planes_installed(s, rc);
+    return rc;
+}
+
+int gipuma_hip_seed_planes(gipuma_hip_session *s, const float *prior_dev, int prior_rows, int prior_cols, int shift)
+{
+    FORWARD(s, seed_planes, prior_dev, prior_rows, prior_cols, shift);
+    if (!s || !prior_dev) return fail(GIPUMA_HIP_ERR_ARG, "null argument");
+    if (prior_rows < 1 || prior_cols < 1 || shift < 0 || shift > 15)
+        return fail(GIPUMA_HIP_ERR_ARG, "seed: prior_rows / prior_cols must be positive and shift in 0..15");
+    // (each lane reads the prior's pixel it covers and writes its own plane: only the same pixel may be both)
+    if (shift != 0 && prior_dev == (const float *)s->norm4)
+        return fail(GIPUMA_HIP_ERR_ARG, "seed: a session's own planes can seed it at shift 0 only");
+    HIP_OK(hipSetDevice(s->device));
+    int rc = new_planes_reset(s);
+    if (!rc) {
+        const int n = s->rows * s->cols;
+        hipLaunchKernelGGL(pm::seed_kernel, dim3((n + pm::kThreads - 1) / pm::kThreads), dim3(pm::kThreads), 0, s->stream, s->dp,
+                           s->norm4, (const float4 *)prior_dev, prior_rows, prior_cols, shift);
+        HIP_OK(hipGetLastError());
+        rc = launch_dense(s, false, s->norm4, s->cost);
     }
-    if (s->seen_pos) HIP_OK(hipMemsetAsync(s->seen_pos, 0, (size_t)s->rows * s->cols, s->stream));  // rule (S): new planes
-    const int rc = launch_dense(s, true, s->norm4, s->cost);
-    if (!rc) s->costs_trusted = true;
-    s->finalized = false;
-    s->prev1 = s->prev2 = -1;
-    s->push_valid = -1;
+    new_planes_installed(s, rc);
     return rc;
 }
 
@@ -1236,15 +1276,15 @@ int gipuma_hip_state_device_ptrs(gipuma_hip_session *s, float **norm4_dev, float
     return 0;
 }
 
-int gipuma_hip_solve(gipuma_hip_session *s, gipuma_hip_timing *timing)
+// gipuma_hip_solve (prior_dev == nullptr: random planes) and gipuma_hip_solve_seeded
+static int solve_from(gipuma_hip_session *s, gipuma_hip_timing *timing, const float *prior_dev, int prior_rows, int prior_cols,
+                      int shift)
 {
-    FORWARD(s, solve, timing);
-    if (!s) return fail(GIPUMA_HIP_ERR_ARG, "null session");
     HIP_OK(hipSetDevice(s->device));
     int rc;
     int launches = 0;
     HIP_OK(hipEventRecord(s->ev[0], s->stream));
-    if ((rc = gipuma_hip_init_planes(s))) return rc;
+    if ((rc = prior_dev ? gipuma_hip_seed_planes(s, prior_dev, prior_rows, prior_cols, shift) : gipuma_hip_init_planes(s))) return rc;
     HIP_OK(hipEventRecord(s->ev[1], s->stream));
     const size_t n_lev = (timing || s->launch_times) ? (size_t)(2 * s->iterations + 1) : 0;
     while (s->lev.size() < n_lev) {
@@ -1326,6 +1366,21 @@ int gipuma_hip_solve(gipuma_hip_session *s, gipuma_hip_timing *timing)
         }
     }
     return 0;
+}
+
+int gipuma_hip_solve(gipuma_hip_session *s, gipuma_hip_timing *timing)
+{
+    FORWARD(s, solve, timing);
+    if (!s) return fail(GIPUMA_HIP_ERR_ARG, "null session");
+    return solve_from(s, timing, nullptr, 0, 0, 0);
+}
+
+int gipuma_hip_solve_seeded(gipuma_hip_session *s, const float *prior_dev, int prior_rows, int prior_cols, int shift,
+                            gipuma_hip_timing *timing)
+{
+    FORWARD(s, solve_seeded, prior_dev, prior_rows, prior_cols, shift, timing);
+    if (!s || !prior_dev) return fail(GIPUMA_HIP_ERR_ARG, "null argument");
+    return solve_from(s, timing, prior_dev, prior_rows, prior_cols, shift);
 }
 
 int gipuma_hip_launch_times(gipuma_hip_session *s, float *ms_half_sweep, int capacity, int *n_half_sweeps, int *n_pushed)

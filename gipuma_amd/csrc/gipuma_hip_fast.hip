@@ -24,6 +24,8 @@
 #define gipuma_hip_set_state gipuma_hipf_set_state
 #define gipuma_hip_state_device_ptrs gipuma_hipf_state_device_ptrs
 #define gipuma_hip_solve gipuma_hipf_solve
+#define gipuma_hip_seed_planes gipuma_hipf_seed_planes
+#define gipuma_hip_solve_seeded gipuma_hipf_solve_seeded
 #define gipuma_hip_launch_times gipuma_hipf_launch_times
 #define gipuma_hip_group_times gipuma_hipf_group_times
 #define gipuma_hip_schedule gipuma_hipf_schedule

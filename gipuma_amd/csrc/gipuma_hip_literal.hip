@@ -25,6 +25,8 @@
 #define gipuma_hip_set_state gipuma_hipl_set_state
 #define gipuma_hip_state_device_ptrs gipuma_hipl_state_device_ptrs
 #define gipuma_hip_solve gipuma_hipl_solve
+#define gipuma_hip_seed_planes gipuma_hipl_seed_planes
+#define gipuma_hip_solve_seeded gipuma_hipl_solve_seeded
 #define gipuma_hip_launch_times gipuma_hipl_launch_times
 #define gipuma_hip_group_times gipuma_hipl_group_times
 #define gipuma_hip_schedule gipuma_hipl_schedule

@@ -1205,4 +1205,35 @@ __global__ __launch_bounds__(kThreads) void finalize_kernel(const Problem *__res
     norm4[PM_AT(P, center, PM_NP(P), kChkNorm4)] = make_float4(w.x, w.y, w.z, depth);
 }
 
+// A start from something known instead of random_plane: the prior is a (world normal, depth) map as
+// finalize_kernel leaves it, at 1 / 2^shift of this session's resolution.  Per pixel: the prior's normal back in
+// reference-camera coordinates (R_orig = the transpose of R_orig_inv), flipped towards the camera, and the plane through
+// the pixel's own ray at the prior's depth; where the prior is not usable (non-finite, depth outside the range, zero
+// normal) exactly the plane random_plane draws.  The costs come from the init kernel that follows (given planes).
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+__global__ __launch_bounds__(kThreads) void seed_kernel(const Problem *__restrict__ P, float4 *__restrict__ norm4,
+                                                        const float4 *__restrict__ prior, int prior_rows, int prior_cols,
+                                                        int shift)
+{
+    const int n = P->rows * P->cols;
+    const int center = blockIdx.x * kThreads + threadIdx.x;
+    if (center >= n) return;
+    const int py = center / P->cols, px = center - py * P->cols;
+    const RefCam &rc = P->rc;
+    const float4 q = prior[(size_t)min(py >> shift, prior_rows - 1) * (size_t)prior_cols + (size_t)min(px >> shift, prior_cols - 1)];
+    const bool ok = finite_f32(q.x) && finite_f32(q.y) && finite_f32(q.z) && finite_f32(q.w) && rc.depth_min <= q.w &&
+                    q.w <= rc.depth_max && (q.x * q.x + q.y * q.y) + q.z * q.z > 0.0f;
+    float4 pl;
+    if (ok) {
+        const float *Ri = rc.R_orig_inv;
+        const float Rt[9] = {Ri[0], Ri[3], Ri[6], Ri[1], Ri[4], Ri[7], Ri[2], Ri[5], Ri[8]};
+        const Vec3 nw = {q.x, q.y, q.z};
+        const Vec3 nc = on_hemisphere(matvec(Rt, nw), view_vector(rc, px, py));
+        pl = make_float4(nc.x, nc.y, nc.z, plane_d(rc, nc, px, py, q.w));
+    } else {
+        pl = random_plane(P, px, py);
+    }
+    norm4[PM_AT(P, center, PM_NP(P), kChkNorm4)] = pl;
+}
+
 }  // namespace pm

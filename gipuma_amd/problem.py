@@ -237,6 +237,7 @@ class Session:
         if self.h:
             self.lib.gipuma_hip_destroy(self.h)
             self.h = C.c_void_p()
+        self._prior_keep = None
 
     def __enter__(self):
         return self
@@ -263,6 +264,49 @@ class Session:
         abi.check(self.lib, self.lib.gipuma_hip_solve(self.h, C.byref(t) if timing else None),
                   "gipuma_hip_solve")
         return t
+
+    def _prior(self, prior, prior_rows, prior_cols):
+        """(device address, rows, cols) of a prior map given as a device address (with its size), a device tensor or a
+        host array of (rows, cols, 4) float32 -- e.g. normals.dmb and disp.dmb stacked --, which is uploaded first"""
+        if isinstance(prior, int):
+            if prior_rows is None or prior_cols is None:
+                raise ValueError("a prior given by device address needs prior_rows and prior_cols")
+            return prior, int(prior_rows), int(prior_cols)
+        if hasattr(prior, "data_ptr"):  # a torch tensor resident on the session's device
+            if not prior.is_cuda or prior.dtype.itemsize != 4 or not prior.is_contiguous() or prior.shape[-1] != 4:
+                raise ValueError("a prior tensor must be a contiguous float32 (rows, cols, 4) device tensor")
+            self._prior_keep = prior
+            return prior.data_ptr(), int(prior.shape[0]), int(prior.shape[1])
+        import torch
+        host = np.ascontiguousarray(prior, dtype=np.float32)
+        if host.ndim != 3 or host.shape[2] != 4:
+            raise ValueError("a prior array must be (rows, cols, 4): (n_world.xyz, depth)")
+        dev = torch.from_numpy(host).to("cuda:%d" % self.gs.desc.device_id)
+        torch.cuda.synchronize(dev.device)  # (the session's stream does not wait for torch's)
+        self._prior_keep = dev  # alive until the next seed or close()
+        return dev.data_ptr(), host.shape[0], host.shape[1]
+
+    def seed_planes(self, prior, shift=0, prior_rows=None, prior_cols=None):
+        """gipuma_hip_seed_planes: planes and costs from a (n_world, depth) map at 1 / 2**shift of this session's
+        resolution instead of random planes.  `prior`: see _prior.  Asynchronous; a prior given by address
+        or tensor must be complete and stay untouched until the session is synchronised."""
+        ptr, pr, pc = self._prior(prior, prior_rows, prior_cols)
+        abi.check(self.lib, self.lib.gipuma_hip_seed_planes(self.h, ptr, pr, pc, shift), "gipuma_hip_seed_planes")
+
+    def solve_seeded(self, prior, shift=0, timing=True, prior_rows=None, prior_cols=None):
+        """gipuma_hip_solve_seeded: seed_planes + the session's iterations + finalize"""
+        ptr, pr, pc = self._prior(prior, prior_rows, prior_cols)
+        t = abi.Timing()
+        abi.check(self.lib, self.lib.gipuma_hip_solve_seeded(self.h, ptr, pr, pc, shift, C.byref(t) if timing else None),
+                  "gipuma_hip_solve_seeded")
+        return t
+
+    def state_device_ptrs(self):
+        """(norm4, cost) device addresses of the session's state planes (gipuma_hip_state_device_ptrs)"""
+        n4, c = C.c_void_p(), C.c_void_p()
+        abi.check(self.lib, self.lib.gipuma_hip_state_device_ptrs(self.h, C.byref(n4), C.byref(c)),
+                  "gipuma_hip_state_device_ptrs")
+        return n4.value, c.value
 
     def launch_times(self):
         """(ms per half-sweep of the last timed solve, number of leading half-sweeps that include a

@@ -235,6 +235,45 @@ int gipuma_hip_schedule(gipuma_hip_session *s, int info[4]);
 int gipuma_hip_run(const gipuma_hip_desc *desc, float *norm4_out, float *cost_out,
                    gipuma_hip_timing *timing);
 
+/* ---- a start from a known depth / normal map instead of random planes ----
+ * The prior is a DEVICE buffer of prior_rows x prior_cols float4 in the public result form (n_world.xyz, depth) -- what
+ * gipuma_hip_finalize leaves in norm4 and what disp.dmb + normals.dmb hold --, covering the frame at 1 / 2^shift of the
+ * session's resolution (shift >= 0; depth is the camera-frame z, and R, C of the reference camera are the same on every
+ * pyramid level, so neither needs rescaling between levels).  For pixel (x, y), in float32 without contraction:
+ *     (nw, z) = prior[min(y >> shift, prior_rows - 1)][min(x >> shift, prior_cols - 1)]
+ *     usable:  nw and z finite,  depth_min <= z <= depth_max of camera 0,  (nw.x nw.x + nw.y nw.y) + nw.z nw.z > 0
+ *     plane = (n, d) with n = R_orig nw flipped towards the camera (vecOnHemisphere_cu, gipuma.cu:131-137) and d of the
+ *             plane through the pixel's own ray at depth z (getD_cu, gipuma.cu:96-111); the normal is not renormalised
+ *     not usable:  exactly the plane gipuma_hip_init_planes draws for (x, y) with the session's seed
+ *     cost  = the multi-view cost of that plane
+ * Afterwards the session is in the state gipuma_hip_init_planes leaves (costs known, hints and history cleared), so the
+ * half-sweeps that follow run the session's schedule (gipuma_hip_schedule) like those of a plain solve.  A
+ * finalize -> seed round trip at shift 0 returns the planes up to rounding, not in every bit.  The prior must be
+ * COMPLETE when the call is made (as for the images: the session's stream does not wait for the stream that wrote it)
+ * and must stay untouched until the seed has run; a session's own norm4 may seed it at shift 0 only.
+ * Enqueues on the session's stream and does not synchronise. */
+int gipuma_hip_seed_planes(gipuma_hip_session *s, const float *prior_dev, int prior_rows, int prior_cols, int shift);
+/* gipuma_hip_solve with gipuma_hip_seed_planes in place of the random initialisation: seed + the session's iterations x
+ * (black, red) + finalize.  Half-sweeps are numbered from iteration 0, so the random draws of a pyramid level do not depend
+ * on the levels below it.  iterations = 0 is legal and gives the finalized seed.  timing->ms_init is the seed's time.
+ * Does not synchronise the host unless `timing` is non-NULL. */
+int gipuma_hip_solve_seeded(gipuma_hip_session *s, const float *prior_dev, int prior_rows, int prior_cols, int shift,
+                            gipuma_hip_timing *timing);
+
+/* ---- one pyramid level of an image plane ----
+ * Reduces the device plane rows x cols (pitch in floats, channels 1 or 4) to (rows >> 1) x (cols >> 1); a last odd row
+ * or column is dropped.  Per channel
+ *     out[Y][X] = floorf(((in[2Y][2X] + in[2Y][2X+1]) + (in[2Y+1][2X] + in[2Y+1][2X+1])) * 0.25f + 0.5f)
+ * For integer-valued 0..255 planes every step is exact in fp32 and the output is integer-valued again: the coarse plane
+ * passes the 8-bit test of gipuma_hip_create like its parent.  Coarse pixel X covers fine pixels 2X, 2X+1, so the camera
+ * of the level is that of S P with S = [[1/2, 0, -1/4], [0, 1/2, -1/4], [0, 0, 1]] (gipuma_amd/pyramid.py
+ * level_projection).  Runs on `stream` and does not synchronise; with stream == NULL it runs on the null stream and
+ * returns when the plane is complete. */
+int gipuma_hip_downsample(const float *src_dev, int rows, int cols, int pitch, int channels, float *dst_dev,
+                          int dst_pitch, int device_id, void *stream);
+/* (the name design documents use for it: the factor is part of the contract, not of the symbol) */
+#define gipuma_hip_downsample2 gipuma_hip_downsample
+
 /* ---- depth-map fusion: per-view (n_world, depth) planes -> one point cloud ----
  * The step the reference's scripts hand to an external tool after the per-view solves (scripts/dtu_fast.sh:23-26,
  * --disp_thresh / --normal_thresh / --num_consistent).  No parity with that tool is claimed; the contract is

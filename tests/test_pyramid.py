@@ -1,0 +1,452 @@
+"""Coarse-to-fine solve: the pyramid level of an image (pyr::downsample2_kernel), the seed of a session
+from a (world normal, depth) map (pm::seed_kernel) and the hierarchy built from them (gipuma_amd.pyramid, batch
+--levels), against the numpy float32 restatement of the contract (tests/pyramid_ref.py) and the CPU oracle -- bit for bit
+unless said otherwise."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+from gipuma_amd import abi, dmb, pyramid, synth
+from gipuma_amd.cameras import decompose_projection
+from gipuma_amd.problem import GlobalState, Session, runcuda
+from tests import oracle_lib, pyramid_ref
+from tests.oracle_lib import OracleState
+
+f32 = np.float32
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def assert_same(a, b, what):
+    a, b = bits(a), bits(b)
+    if not np.array_equal(a, b):
+        bad = np.argwhere(a != b)
+        raise AssertionError("%s: %d of %d values differ, first at %s: %r vs %r"
+                             % (what, len(bad), a.size, tuple(bad[0]), a.view(np.float32)[tuple(bad[0])],
+                                b.view(np.float32)[tuple(bad[0])]))
+
+
+def in_tolerance(a, b):  # (tests/test_fast_mode.py)
+    d_rel = np.abs(a[..., 3] - b[..., 3]) / np.maximum(np.abs(b[..., 3]), 1e-30)
+    n_err = np.abs(a[..., :3] - b[..., :3]).max(-1)
+    return float(((d_rel < 1e-4) & (n_err < 1e-3)).mean())
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# CPU
+# ------------------------------------------------------------------------------------------------------------------
+def test_level_projection_halves_pixel_coordinates_and_keeps_the_pose():
+    """world points in front of the DTU cameras project to (x - 1/2) / 2 of their fine pixel (1e-9 relative, float64);
+    R and C of the decomposed level cameras equal the fine ones to 1e-12"""
+    rng = np.random.default_rng(3)
+    allP = synth.dtu_projection_matrices()
+    for k in sorted(allP)[:8]:
+        P = np.asarray(allP[k], dtype=np.float64)
+        K, R, Cc = decompose_projection(P)
+        # points 400 .. 800 in front of the camera, inside a 1600x1200 frame
+        z = rng.uniform(400.0, 800.0, size=50)
+        px = np.stack([rng.uniform(0, 1600, 50) * z, rng.uniform(0, 1200, 50) * z, z])
+        X = R.T @ (np.linalg.inv(K) @ px) + Cc[:, None]
+        Xh = np.vstack([X, np.ones(50)])
+        fine = P @ Xh
+        fine = fine[:2] / fine[2]
+        for level in (1, 2, 3):
+            Pl = pyramid.level_projection(P, level)
+            want = fine
+            for _ in range(level):
+                want = (want - 0.5) / 2.0
+            got = Pl @ Xh
+            got = got[:2] / got[2]
+            assert np.abs(got - want).max() <= 1e-9 * np.abs(want).max()
+            Kl, Rl, Cl = decompose_projection(Pl)
+            assert np.abs(Rl - R).max() <= 1e-12
+            assert np.abs(Cl - Cc).max() <= 1e-12 * max(1.0, np.abs(Cc).max())
+    assert np.array_equal(pyramid.level_projection(P, 0), P)
+
+
+def test_restated_downsample_of_integer_planes_is_the_integer_mean():
+    rng = np.random.default_rng(5)
+    for shape in ((48, 64), (37, 45), (30, 22, 4), (2, 2), (3, 3)):
+        a = rng.integers(0, 256, size=shape)
+        got = pyramid_ref.downsample2(a.astype(f32))
+        r, c = shape[0] >> 1, shape[1] >> 1
+        a = a.astype(np.int64)
+        want = (a[0:2 * r:2, 0:2 * c:2] + a[0:2 * r:2, 1:2 * c:2] + a[1:2 * r:2, 0:2 * c:2] + a[1:2 * r:2, 1:2 * c:2] + 2) >> 2
+        assert got.shape == want.shape and got.dtype == np.float32
+        assert np.array_equal(got, np.floor(got)) and np.array_equal(got.astype(np.int64), want)
+    ext = np.array([[255, 255], [255, 255]], dtype=f32)
+    assert pyramid_ref.downsample2(ext)[0, 0] == 255 and pyramid_ref.downsample2(ext * 0)[0, 0] == 0
+
+
+def test_restated_geometry_equals_the_oracle_s_unit_functions(oracle, tiny_problem):
+    """view vector and plane offset of the restatement against gipuma_oracle_view_vector / _plane_d, every pixel"""
+    gs, _ = tiny_problem
+    cam = gs.cameras.c_array[0]
+    vv = pyramid_ref.view_vectors(cam, gs.rows, gs.cols)
+    rng = np.random.default_rng(1)
+    n = rng.normal(size=(gs.rows, gs.cols, 3)).astype(f32)
+    depth = rng.uniform(300, 800, size=(gs.rows, gs.cols)).astype(f32)
+    d = pyramid_ref.plane_d(cam, n, depth, gs.rows, gs.cols)
+    v = np.zeros(3, dtype=f32)
+    for y in range(gs.rows):
+        for x in range(gs.cols):
+            oracle.gipuma_oracle_view_vector(C.byref(cam), x, y, oracle_lib.fptr(v))
+            assert np.array_equal(bits(v), bits(vv[y, x])), (x, y)
+            nn = np.ascontiguousarray(n[y, x])
+            assert bits(f32(oracle.gipuma_oracle_plane_d(C.byref(cam), oracle_lib.fptr(nn), x, y, float(depth[y, x])))) == \
+                bits(d[y, x]), (x, y)
+
+
+def test_new_entry_points_validate_their_arguments():
+    lib = abi.load_library()
+    assert lib.gipuma_hip_seed_planes(None, None, 1, 1, 0) == abi.ERR_ARG
+    assert lib.gipuma_hip_solve_seeded(None, None, 1, 1, 0, None) == abi.ERR_ARG
+    assert lib.gipuma_hip_downsample(None, 4, 4, 4, 1, None, 2, 0, None) == abi.ERR_ARG
+    assert lib.gipuma_hip_downsample(8, 4, 4, 4, 3, 8, 2, 0, None) == abi.ERR_UNSUPPORTED
+    assert lib.gipuma_hip_downsample(8, 4, 4, 3, 1, 8, 2, 0, None) == abi.ERR_ARG  # pitch < cols
+    assert lib.gipuma_hip_downsample(8, 4, 4, 4, 1, 8, 1, 0, None) == abi.ERR_ARG  # dst_pitch < cols >> 1
+    assert lib.gipuma_hip_downsample(8, 1, 4, 4, 1, 8, 2, 0, None) == abi.ERR_ARG  # no output row
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# GPU: the pyramid level of an image
+# ------------------------------------------------------------------------------------------------------------------
+def _torch():
+    import torch
+    return torch
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows,cols,pitch_extra,channels", [
+    (48, 64, 0, 1), (37, 45, 0, 1), (37, 45, 3, 1), (50, 70, 2, 1), (51, 66, 4, 1), (2, 2, 0, 1), (3, 5, 1, 1),
+    (48, 64, 0, 4), (37, 45, 0, 4), (37, 45, 8, 4), (21, 33, 3, 4), (1200, 1600, 0, 1), (1200, 1600, 0, 4)])
+def test_downsample_equals_the_restatement(hip, rows, cols, pitch_extra, channels):
+    """even and odd sizes, pitch > cols (aligned to 16, 8 and 4 bytes: every load width), gray and colour, 1600x1200"""
+    torch = _torch()
+    rng = np.random.default_rng(rows * 131 + cols)
+    shape = (rows, cols) + ((4,) if channels == 4 else ())
+    host = rng.integers(0, 256, size=shape).astype(f32)
+    pitch = cols * channels + pitch_extra
+    buf = torch.full((rows, pitch), -7.0, dtype=torch.float32, device="cuda:0")
+    view = buf[:, :cols * channels]
+    view.copy_(torch.from_numpy(host.reshape(rows, cols * channels)))
+    src = view if channels == 1 else torch.as_strided(buf, (rows, cols, 4), (pitch, 4, 1))
+    got = pyramid.downsample(src)
+    torch.cuda.synchronize()
+    assert_same(got.cpu().numpy(), pyramid_ref.downsample2(host), "downsample %dx%d pitch %d ch %d" % (cols, rows, pitch, channels))
+    # a destination with a pitch of its own: nothing outside the output pixels is written
+    orows, ocols = rows >> 1, cols >> 1
+    dpitch = ocols * channels + 5
+    dst = torch.full((orows, dpitch), -3.0, dtype=torch.float32, device="cuda:0")
+    out = dst[:, :ocols] if channels == 1 else torch.as_strided(dst, (orows, ocols, 4), (dpitch, 4, 1))
+    pyramid.downsample(src, out=out)
+    torch.cuda.synchronize()
+    d = dst.cpu().numpy()
+    assert_same(d[:, :ocols * channels].reshape(got.shape), pyramid_ref.downsample2(host), "downsample into a pitched plane")
+    assert (d[:, ocols * channels:] == -3.0).all()
+
+
+@pytest.mark.gpu
+def test_downsample_two_levels_in_a_row_and_float_planes(hip):
+    torch = _torch()
+    rng = np.random.default_rng(11)
+    host = rng.integers(0, 256, size=(203, 301)).astype(f32)
+    l1 = pyramid.downsample(torch.from_numpy(host).cuda())
+    l2 = pyramid.downsample(l1)
+    torch.cuda.synchronize()
+    r1 = pyramid_ref.downsample2(host)
+    assert_same(l1.cpu().numpy(), r1, "level 1")
+    assert_same(l2.cpu().numpy(), pyramid_ref.downsample2(r1), "level 2")
+    assert l2.shape == (50, 75)
+    fl = rng.uniform(0, 255, size=(64, 96)).astype(f32)  # not integer valued: still the contract's formula
+    assert_same(pyramid.downsample(torch.from_numpy(fl).cuda()).cpu().numpy(), pyramid_ref.downsample2(fl), "float plane")
+    with pyramid.ScanPyramid([torch.from_numpy(host).cuda()], 3) as pyr:
+        assert pyr.size(2) == (50, 75) and pyr.device_ms > 0
+        assert_same(pyr.planes[2][0].cpu().numpy(), pyramid_ref.downsample2(r1), "ScanPyramid level 2")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# GPU: the seed
+# ------------------------------------------------------------------------------------------------------------------
+def _perturbed_prior(gs, info, shift, box):
+    """a solved level (HIP, plain solve) at 1 / 2^shift of gs, perturbed so that every branch of the seed is reached"""
+    if shift:
+        g = pyramid_ref.level_problem(gs, info, shift, 3)
+        prior, _ = runcuda(g)
+    else:
+        prior, _ = runcuda(gs)
+    prior = prior.copy()
+    dmin, dmax = f32(gs.cameras.c_array[0].depth_min), f32(gs.cameras.c_array[0].depth_max)
+    prior[1, 2, 3] = np.nan
+    prior[2, 3, 3] = np.inf
+    prior[3, 4, 3] = -np.inf
+    prior[4, 5, 1] = np.nan
+    prior[5, 6, 0] = np.inf
+    prior[6, 7, 3] = 0.0
+    prior[7, 8, 3] = dmin * f32(0.5)
+    prior[8, 9, 3] = dmax * f32(1.5)
+    prior[9, 10, :3] = 0.0
+    prior[10, 11, 3] = dmin      # the bounds themselves are usable
+    prior[11, 12, 3] = dmax
+    prior[12:16, 13:20, :3] *= f32(-1.0)  # normals that need the hemisphere flip
+    prior[16, 14, :3] *= f32(3.0)  # not renormalised
+    named = dict(nan_depth=(1, 2), inf_depth=(2, 3), nan_normal=(4, 5), zero_depth=(6, 7), below_min=(7, 8),
+                 above_max=(8, 9), zero_normal=(9, 10))
+    return prior, named
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shift", [0, 1])
+def test_seed_planes_equals_the_restatement_in_every_branch(hip, shift):
+    """odd fine size (the prior index clamps at shift 1), every rejection branch, the hemisphere flip; planes and costs bit
+    for bit; fallback pixels equal the oracle's init planes; afterwards the session sweeps like an initialised one"""
+    gs, info = synth.build_problem(synth.tiny_config(cols=161, rows=113, n_src=4, blocksize=11, iterations=2, n_best=3))
+    prior, named = _perturbed_prior(gs, info, shift, 11)
+    if shift:
+        assert prior.shape[:2] == (56, 80) and (gs.rows - 1) >> 1 == 56 and (gs.cols - 1) >> 1 == 80  # clamps
+    planes, cost, inf = pyramid_ref.seed_planes(gs, prior, shift)
+    fb = inf["fallback"]
+    for name, (y, x) in named.items():  # each branch was taken by at least one pixel
+        assert fb[y << shift, x << shift], name
+    for y, x in ((10, 11), (11, 12), (16, 14)):
+        assert not fb[y << shift, x << shift]
+    region = (slice(12 << shift, 16 << shift), slice(13 << shift, 20 << shift))
+    assert (inf["flipped"] | fb)[region].all() and inf["flipped"][region].any() and (~inf["flipped"] & ~fb).any()
+    assert 0 < fb.mean() < 0.05
+    o = OracleState(gs)
+    o.init_planes()
+    assert_same(planes[fb], o.norm4[fb], "fallback pixels == gipuma_oracle_init_planes")
+    assert_same(cost[fb], o.cost[fb], "fallback costs")
+    with Session(gs) as s, Session(gs, fast=True) as sf, Session(gs, literal=True) as sl:
+        s.seed_planes(prior, shift)
+        n4, c = s.get_state()
+        assert_same(n4, planes, "seed planes shift %d" % shift)
+        assert_same(c, cost, "seed costs shift %d" % shift)
+        sf.seed_planes(prior, shift)
+        assert_same(sf.get_state()[0], planes, "FAST seed planes")
+        sl.seed_planes(prior, shift)
+        assert_same(sl.get_state()[0], planes, "LITERAL seed planes")
+        # stepped: seed, sweeps, finalize == the one call == restatement + oracle
+        for it in range(gs.params.iterations):
+            s.sweep(it, abi.BLACK)
+            s.sweep(it, abi.RED)
+        s.finalize()
+        stepped = s.get_state()
+        s.solve_seeded(prior, shift)
+        one = s.get_state()
+    r_n4, r_c, _ = pyramid_ref.solve_seeded(gs, prior, shift)
+    for got, what in ((stepped, "stepped"), (one, "solve_seeded")):
+        assert_same(got[0], r_n4, "%s norm4 shift %d" % (what, shift))
+        assert_same(got[1], r_c, "%s cost shift %d" % (what, shift))
+
+
+@pytest.mark.gpu
+def test_seed_from_a_device_pointer_and_round_trip(hip):
+    """the prior by device address (another session's finalized planes, no host round trip) equals the host array; a
+    finalize -> seed round trip at shift 0 returns the planes up to rounding; iterations = 0 gives the finalized seed"""
+    gs, info = synth.build_problem(synth.tiny_config(cols=96, rows=64, n_src=3, blocksize=11, iterations=2, n_best=2))
+    with Session(gs) as a, Session(gs) as b:
+        a.init_planes()
+        for colour in (abi.BLACK, abi.RED):
+            a.sweep(0, colour)
+        planes, cost = a.get_state()
+        a.finalize()
+        a.sync()
+        prior, _ = a.get_state()
+        b.seed_planes(a.state_device_ptrs()[0], 0, prior_rows=gs.rows, prior_cols=gs.cols)
+        n_dev, c_dev = b.get_state()
+        b.seed_planes(prior, 0)
+        n_host, c_host = b.get_state()
+        assert_same(n_dev, n_host, "device prior == host prior")
+        assert_same(c_dev, c_host, "device prior == host prior (cost)")
+        # (finalize writes depth 0 where the cost is MAXCOST, and a propagated plane may leave the depth range at its pixel:
+        #  those fall back.  The rest returns up to rounding: the normal through R_orig R_orig^-1, a few ulp; the offset
+        #  through depth = -d fx / (n . ray), whose conditioning has no bound for grazing planes -- judged as a share)
+        ok = ~pyramid_ref.seed_planes(gs, prior, 0)[2]["fallback"]
+        assert ok.mean() > 0.9
+        assert np.allclose(n_host[ok][:, :3], planes[ok][:, :3], atol=2e-6)
+        assert np.isclose(n_host[ok][:, 3], planes[ok][:, 3], rtol=1e-4).mean() > 0.99
+        assert not np.array_equal(bits(n_host[ok]), bits(planes[ok]))  # ... and not in every bit
+        assert b.lib.gipuma_hip_seed_planes(b.h, b.state_device_ptrs()[0], gs.rows, gs.cols, 1) == abi.ERR_ARG
+    g0 = pyramid_ref.level_problem(gs, info, 0, 0)
+    with Session(g0) as s:
+        s.solve_seeded(prior, 0)
+        n4, c = s.get_state()
+    r_n4, r_c, _ = pyramid_ref.solve_seeded(g0, prior, 0)
+    assert_same(n4, r_n4, "iterations = 0: the finalized seed")
+    assert_same(c, r_c, "iterations = 0: cost")
+
+
+SEEDED_CASES = [
+    ("box11", dict(cols=832, rows=640, blocksize=11, n_src=4, n_best=3, iterations=2), False, None),
+    ("box15", dict(cols=832, rows=640, iterations=2), False, None),
+    ("box15-literal", dict(cols=832, rows=640, iterations=1), False, 7),
+    ("colour", dict(cols=208, rows=160, iterations=2), True, None),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,over,colour,flavour", SEEDED_CASES, ids=[c[0] for c in SEEDED_CASES])
+def test_solve_seeded_equals_the_oracle_from_the_restated_seed(hip, name, over, colour, flavour):
+    """config C's cameras and parameters at a size where the pushed, column-per-lane and fused kernels run (832x640, as the
+    whole-frame parity tests), seeded from the half-resolution level's solve: final maps and costs of every pixel"""
+    gs, info = synth.build_problem("C", colour=colour, **over)
+    literal = flavour == 7
+    coarse = pyramid_ref.level_problem(gs, info, 1, 3)
+    prior, _ = runcuda(coarse, literal=literal)
+    with Session(gs, literal=literal) as s:
+        sched = s.schedule()
+        s.solve_seeded(prior, 1)
+        n4, c = s.get_state()
+        assert s.schedule() == sched
+    print("%s: schedule %r" % (name, sched))
+    r_n4, r_c, inf = pyramid_ref.solve_seeded(gs, prior, 1, flavour)
+    print("%s: %.4f of the pixels seeded by the random fallback" % (name, inf["fallback"].mean()))
+    assert_same(n4, r_n4, "%s norm4" % name)
+    assert_same(c, r_c, "%s cost" % name)
+
+
+@pytest.mark.gpu
+def test_fast_mode_seeded_solve_is_judged_like_a_plain_one(hip):
+    """config C 320x256 (tests/test_fast_mode.py: floor 0.999 of the pixels inside 1e-4 relative depth / 1e-3 normal of the
+    default mode's result): the same floor for the seeded solve, from the same prior"""
+    gs, info = synth.build_problem("C", cols=320, rows=256)
+    prior, _ = runcuda(pyramid_ref.level_problem(gs, info, 1, 8))
+    out = []
+    for fast in (False, True):
+        with Session(gs, fast=fast) as s:
+            s.solve_seeded(prior, 1)
+            out.append(s.get_state()[0])
+    got = in_tolerance(out[1], out[0])
+    print("fast vs default, seeded config C 320x256: %.4f of the pixels inside the tolerance" % got)
+    assert got >= 0.999
+
+
+@pytest.mark.gpu
+def test_a_seeded_session_solves_plainly_like_a_fresh_one(hip):
+    gs, info = synth.build_problem(synth.tiny_config(cols=160, rows=112, n_src=4, blocksize=15, iterations=3, n_best=3))
+    prior, _ = runcuda(pyramid_ref.level_problem(gs, info, 1, 2))
+    with Session(gs) as fresh:
+        plain_schedule = fresh.schedule()
+        fresh.solve()
+        want = fresh.get_state()
+    with Session(gs) as s:
+        s.solve_seeded(prior, 1)
+        assert s.schedule() == plain_schedule
+        s.solve()
+        got = s.get_state()
+        assert s.schedule() == plain_schedule
+    assert_same(got[0], want[0], "plain solve after a seeded one: norm4")
+    assert_same(got[1], want[1], "plain solve after a seeded one: cost")
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# GPU: the whole hierarchy
+# ------------------------------------------------------------------------------------------------------------------
+def _quality_problem(scene, iterations=8):
+    """the problem of DESIGN.md 12's table: DTU geometry, 320x240, box 11, 4 source views, best-3, seed 1"""
+    return synth.build_problem(synth.tiny_config(cols=320, rows=240, n_src=4, blocksize=11, iterations=iterations, n_best=3),
+                               scene=scene)
+
+
+def _solve_view(gs, info, level_iterations, mode="exact"):
+    torch = _torch()
+    dev = [torch.from_numpy(np.ascontiguousarray(im)).cuda() for im in gs.images]
+    torch.cuda.synchronize()
+    with pyramid.ScanPyramid(dev, len(level_iterations)) as pyr:
+        return pyramid.solve_view(pyr, info["P_matrices"], [0] + list(gs.selected), gs.params, level_iterations,
+                                  seed=int(gs.desc.seed), mode=mode, cam_scale=info["cam_scale"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("level_iterations", [[8, 2], [3, 2, 1]], ids=["2-levels", "3-levels"])
+def test_solve_view_equals_restatement_plus_oracle(hip, level_iterations):
+    gs, info = _quality_problem("smooth")
+    n4, cost, times = _solve_view(gs, info, level_iterations)
+    assert [t["level"] for t in times] == list(range(len(level_iterations) - 1, -1, -1))
+    assert all(t["ms_total"] > 0 for t in times) and times[-1]["rows"] == 240 and times[0]["cols"] == 320 >> times[0]["level"]
+    r_n4, r_c, _ = pyramid_ref.solve_hierarchy(gs, info, level_iterations)
+    assert_same(n4, r_n4, "solve_view %r norm4" % level_iterations)
+    assert_same(cost, r_c, "solve_view %r cost" % level_iterations)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scene", ["smooth", "steps", "patchy"])
+def test_two_levels_reach_the_quality_of_the_plain_solve(hip, scene):
+    """HIP path, 320x240: the share of ground-truth pixels within 1e-3 relative depth after (8 -> seed -> 2) is at least the
+    plain 8-iteration solve's minus 0.02, the share within 1e-2 at least the plain solve's minus 0.005 (the margins cover the
+    one comparison of DESIGN.md 12's table that lands below the plain solve: patchy, -0.008 at 1e-3); at most 1 % of the
+    pixels are seeded by the random fallback (with the oracle: 0, 0 and 16 of 76 800)"""
+    gs, info = _quality_problem(scene)
+    gt = info["gt_depth"]
+    plain, _ = runcuda(gs)
+    n4, _, _ = _solve_view(gs, info, [8, 2])
+    coarse, _ = runcuda(pyramid_ref.level_problem(gs, info, 1, 8))
+    fallback = pyramid_ref.seed_planes(gs, coarse, 1)[2]["fallback"].mean()
+
+    def share(d, tol):
+        return float((np.abs(d - gt) / gt < tol).mean())
+    q = {tol: (share(plain[..., 3], tol), share(n4[..., 3], tol)) for tol in (1e-3, 1e-2)}
+    print("%s: plain %.4f / %.4f, two levels %.4f / %.4f, fallback %.5f"
+          % (scene, q[1e-3][0], q[1e-2][0], q[1e-3][1], q[1e-2][1], fallback))
+    assert fallback <= 0.01
+    assert q[1e-3][1] >= q[1e-3][0] - 0.02
+    assert q[1e-2][1] >= q[1e-2][0] - 0.005
+
+
+def _write_scan(folder, gs, info):
+    os.makedirs(os.path.join(folder, "img"))
+    os.makedirs(os.path.join(folder, "p"))
+    for i, im in enumerate(gs.images):
+        name = "v%02d.pgm" % i
+        with open(os.path.join(folder, "img", name), "wb") as f:
+            f.write(b"P5\n%d %d\n255\n" % (im.shape[1], im.shape[0]) + im.astype(np.uint8).tobytes())
+        np.savetxt(os.path.join(folder, "p", name + ".P"), np.asarray(info["P_matrices"][i]), fmt="%.17g")
+    return ["--images-folder", os.path.join(folder, "img"), "--p-folder", os.path.join(folder, "p"), "--views", "v00.pgm",
+            "--blocksize=11", "--iterations=3", "--n_best=3", "--depth_min=300", "--depth_max=800", "--min_angle=10",
+            "--max_angle=30", "--max_views=10", "--cam_scale=%r" % info["cam_scale"], "--in_flight=1"]
+
+
+@pytest.mark.gpu
+def test_batch_levels(hip, tmp_path):
+    """batch --levels 2 writes the dumps of pyramid.solve_view on the same plan (== restatement + oracle above) and per-level
+    device times; --levels 1 writes what batch writes without the option, byte for byte"""
+    from gipuma_amd import batch
+    from gipuma_amd.cameras import read_p_file
+    gs, info = synth.build_problem(synth.tiny_config(cols=160, rows=120, n_src=4, blocksize=11, iterations=3, n_best=3))
+    args = _write_scan(str(tmp_path), gs, info)
+    try:
+        read_p_file(os.path.join(str(tmp_path), "p", "v00.pgm.P"))
+    except Exception as e:  # noqa: BLE001
+        pytest.fail("the scan written for this test is not readable: %r" % e)
+    outs = {}
+    for tag, extra in (("plain", []), ("one", ["--levels", "1"]), ("two", ["--levels", "2", "--level_iterations", "3,1"])):
+        out = os.path.join(str(tmp_path), tag)
+        assert batch.main(args + ["--output-folder", out] + extra) == 0
+        outs[tag] = out
+    for f in ("disp.dmb", "normals.dmb", "cost.dmb"):
+        a = open(os.path.join(outs["plain"], "v00", f), "rb").read()
+        assert a == open(os.path.join(outs["one"], "v00", f), "rb").read(), f
+    rep = json.load(open(os.path.join(outs["two"], "batch_rank0.json")))
+    lv = rep["views"][0]["levels"]
+    assert [l["level"] for l in lv] == [1, 0] and [l["iterations"] for l in lv] == [3, 1] and all(l["ms_total"] > 0 for l in lv)
+    assert "levels" not in json.load(open(os.path.join(outs["one"], "batch_rank0.json")))["views"][0]
+    # the same plan through the library's Python layer and through restatement + oracle
+    names = sorted(os.listdir(os.path.join(str(tmp_path), "img")))
+    P_all = [read_p_file(os.path.join(str(tmp_path), "p", n + ".P")) for n in names]
+    host = [batch.read_image(os.path.join(str(tmp_path), "img", n)) for n in names]
+    ap = batch.AlgorithmParameters(iterations=3, n_best=3, depthMin=300.0, depthMax=800.0, min_angle=10.0, max_angle=30.0,
+                                   max_views=10)
+    ap.set_blocksize(11)
+    cs, used, ap_view = batch.plan_views(P_all, names, 0, 160, 120, ap, info["cam_scale"])
+    fine = GlobalState([host[i] for i in used], cs, list(range(1, len(used))), ap_view, seed=1)
+    inf = dict(P_matrices=[P_all[i] for i in used], cam_scale=info["cam_scale"])
+    r_n4, r_c, _ = pyramid_ref.solve_hierarchy(fine, inf, [3, 1])
+    assert_same(dmb.read_dmb(os.path.join(outs["two"], "v00", "disp.dmb")), r_n4[..., 3], "batch --levels 2 disp.dmb")
+    assert_same(dmb.read_dmb(os.path.join(outs["two"], "v00", "normals.dmb")), r_n4[..., :3], "batch --levels 2 normals.dmb")
+    assert_same(dmb.read_dmb(os.path.join(outs["two"], "v00", "cost.dmb")), r_c, "batch --levels 2 cost.dmb")
