@@ -92,6 +92,16 @@ class FusionDesc(C.Structure):
     ]
 
 
+class PriorDesc(C.Structure):
+    """gipuma_hip_prior_desc: the target camera, the solved source views and the knobs of the cross-view prior"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("rows", C.c_int32), ("cols", C.c_int32), ("target", FusionView),
+        ("n_sources", C.c_int32), ("sources", C.POINTER(FusionView)), ("costs", C.POINTER(C.c_void_p)),
+        ("max_cost", C.c_float), ("depth_min", C.c_float), ("depth_max", C.c_float), ("grazing_cos", C.c_float),
+        ("fill", C.c_int32), ("device_id", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
 # every symbol include/gipuma_hip.h declares: (name, restype, argtypes)
 _FP = C.POINTER(C.c_float)
 SYMBOLS = [
@@ -124,6 +134,7 @@ SYMBOLS = [
     ("gipuma_hip_fusion_points", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     ("gipuma_hip_fusion_used", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gipuma_hip_fusion_free", C.c_int, [C.c_void_p]),
+    ("gipuma_hip_prior_from_views", C.c_int, [C.POINTER(PriorDesc), C.c_void_p, C.POINTER(C.c_int64), _FP]),
 ]
 
 _lib = None

@@ -22,6 +22,11 @@ MI355X-first differences from the shell loop:
     gipuma_amd.pyramid) -- the coarse planes are made once per scan, every view solves its coarsest level plainly and
     seeds each finer level from the one below; --level_iterations a,b,.. (coarsest first; default for --levels 2:
     <iterations>,2).  Views are solved one at a time; with --in_flight 1 the report carries per-level device times;
+  * --view_prior N (default 0: off): a view whose selected sources have been solved earlier in this run starts from their
+    results instead of from random planes (gipuma_amd.prior) -- the (normal, depth) maps of up to N solved
+    sources are carried into its camera on the GPU and it runs --prior_iterations iterations from that start; views are
+    taken greedily, the one with the most solved sources next, and solved one at a time; the solved maps stay in HBM for
+    the run (49 views at 1600x1200: 1.9 GB).  With several ranks each rank draws on its own solved views only;
   * --fuse: the results of this run are also fused on the GPU, from memory, into <output>/fused.ply (with
     --disp_thresh / --normal_thresh / --num_consistent and the depth range) -- what the reference's
     scripts leave to an external CUDA tool after the loop (scripts/dtu_fast.sh:56-57).  One process only: with
@@ -118,6 +123,58 @@ def plan_views(P_all, names, ref_idx, cols, rows, ap, cam_scale=1.0):
     return cs, used, ap_view
 
 
+# Iterations of a view that starts from its neighbours' results: the smallest of 1, 2, 3 that met the quality margins on
+# the three 320x240 scenes (tests/test_prior.py).  At 1600x1200 it does NOT hold them: see DESIGN.md 13 and the help text.
+PRIOR_ITERATIONS = 1
+
+
+def solve_with_view_prior(args, names, mine, P_all, dev, rows, cols, ap, dev_index, report, record):
+    """--view_prior: the views of `mine` in gipuma_amd.prior.greedy_order, one at a time.  A view with at least
+    --prior_min_views solved sources starts from the prior of the first --view_prior of them (in selection order) and runs
+    --prior_iterations iterations; any other view runs the plain solve.  Returns the order."""
+    import torch
+    from . import prior as view_prior
+    plans = {}
+    for ref_name in mine:
+        cs, used, ap_view = plan_views(P_all, names, names.index(ref_name), cols, rows, ap, args.cam_scale)
+        if len(used) < 2:
+            report.append({"ref": ref_name, "skipped": "no source view inside the angle cone"})
+            continue
+        plans[ref_name] = (cs, used, ap_view)
+    order = view_prior.greedy_order([n for n in mine if n in plans],
+                                    {n: [names[i] for i in plans[n][1][1:]] for n in plans})
+    kept = {}  # reference name -> (norm4, cost or None) on the device, for the views solved after it
+    for ref_name in order:
+        cs, used, ap_view = plans[ref_name]
+        sources = [names[i] for i in used[1:]]
+        have = [n for n in sources if n in kept][:args.view_prior]
+        tw0 = time.perf_counter()
+        start, pinfo = None, None
+        if len(have) >= args.prior_min_views:
+            with_cost = args.prior_max_cost is not None
+            start, pinfo = view_prior.prior_from_views(
+                P_all[used[0]], [kept[n][0] for n in have], [P_all[names.index(n)] for n in have], args.cam_scale,
+                ap_view.depthMin, ap_view.depthMax, costs=[kept[n][1] for n in have] if with_cost else None,
+                max_cost=args.prior_max_cost, return_info=True, device_id=dev_index)
+            ap_view.iterations = args.prior_iterations
+        imgs = [dev[i] for i in used]
+        gs = GlobalState(imgs, cs, list(range(1, len(used))), ap_view, seed=args.seed,
+                         device_ptrs=[t.data_ptr() for t in imgs], rows=rows, cols=cols, device_id=dev_index,
+                         flags=abi.FLAG_CACHE_IMAGES)
+        with Session(gs, fast=args.mode == "fast", literal=args.mode == "literal") as s:
+            t = s.solve(timing=True) if start is None else s.solve_seeded(start, 0, timing=True)
+            n4, cost = s.get_state()
+        # (kept in HBM for the views solved later: uploaded again from the host copy the dumps need anyway, 31 MB per
+        #  1600x1200 view -- a device-to-device copy out of the session would save that upload)
+        kept[ref_name] = (torch.from_numpy(n4).to("cuda:%d" % dev_index),
+                          torch.from_numpy(cost).to("cuda:%d" % dev_index) if args.prior_max_cost is not None else None)
+        torch.cuda.synchronize()
+        extra = {"iterations": int(ap_view.iterations),
+                 "prior": None if pinfo is None else dict(sources=have, **pinfo)}
+        record(ref_name, sources, tw0, t, n4, cost, extra=extra)
+    return order
+
+
 def main(argv=None):
     pa = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     pa.add_argument("--images-folder", required=True)
@@ -145,6 +202,20 @@ def main(argv=None):
                     help="pyramid levels of a coarse-to-fine solve (1: the plain solve; gipuma_amd.pyramid)")
     pa.add_argument("--level_iterations", default="",
                     help="with --levels > 1: iterations per level, coarsest first (default: <iterations>,2,..,2)")
+    pa.add_argument("--view_prior", type=int, default=0,
+                    help="start a view from the results of up to N of its selected source views that this run (this rank: "
+                         "ranks do not exchange results) has solved already (0: off; gipuma_amd.prior)")
+    pa.add_argument("--prior_iterations", type=int, default=PRIOR_ITERATIONS,
+                    help="with --view_prior: iterations of a view that starts from a prior (the others run --iterations; "
+                         "0: the view's result is the prior itself with the random fallback, finalized).  The default, "
+                         "%d, is the smallest count that matched the plain solve on the 320x240 test scenes; at 1600x1200 "
+                         "it loses quality (config C, share within 1e-2 of ground truth: plain 0.999, 1 it. 0.984, 2 it. "
+                         "0.994, 3 it. 0.999, and the loss compounds from view to view): use 3 there (DESIGN.md 13)"
+                         % PRIOR_ITERATIONS)
+    pa.add_argument("--prior_min_views", type=int, default=2,
+                    help="with --view_prior: solved source views a view needs to start from their prior")
+    pa.add_argument("--prior_max_cost", type=float, default=None,
+                    help="with --view_prior: leave source pixels with a cost above this out of the prior (default: keep all)")
     pa.add_argument("--fuse", action="store_true",
                     help="fuse the views solved in this run into <output-folder>/fused.ply (gipuma_amd.fusion)")
     pa.add_argument("--disp_thresh", type=float, default=0.1, help="with --fuse")
@@ -161,6 +232,16 @@ def main(argv=None):
         [args.iterations] + [2] * (args.levels - 1)
     if args.levels > 1 and len(level_iterations) != args.levels:
         raise SystemExit("--level_iterations needs %d values, coarsest first" % args.levels)
+    if args.view_prior < 0 or args.view_prior > abi.MAX_VIEWS:
+        raise SystemExit("--view_prior must be 0..%d" % abi.MAX_VIEWS)
+    if args.view_prior and args.levels > 1:
+        raise SystemExit("--view_prior cannot be combined with --levels > 1: a view starts either from its coarser level "
+                         "or from its solved neighbours")
+    if args.view_prior and (args.prior_iterations < 0 or args.prior_min_views < 1):
+        raise SystemExit("--prior_iterations must be >= 0 and --prior_min_views >= 1")
+    if args.view_prior and args.view_prior < args.prior_min_views:
+        raise SystemExit("--view_prior %d is below --prior_min_views %d: no view would ever start from a prior"
+                         % (args.view_prior, args.prior_min_views))
     if args.fuse and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--fuse works within one process (there is no exchange of results between ranks): run "
                          "`python -m gipuma_amd.fusion --input-folder %s ...` once every rank is done" % args.output_folder)
@@ -206,7 +287,7 @@ def main(argv=None):
             s.close()
         record(ref_name, sources, tw0, t, n4, cost)
 
-    def record(ref_name, sources, tw0, t, n4, cost, levels=None):
+    def record(ref_name, sources, tw0, t, n4, cost, levels=None, extra=None):
         wall_ms = (time.perf_counter() - tw0) * 1e3  # session set-up + solve (+ what ran beside it) + download
         folder = os.path.join(args.output_folder, os.path.splitext(ref_name)[0])
         os.makedirs(folder, exist_ok=True)
@@ -222,6 +303,8 @@ def main(argv=None):
         if levels is not None:  # (--levels > 1, one view at a time: device times per level, coarsest first)
             ms = sum(lv["ms_total"] for lv in levels)
             entry.update({"levels": levels, "device_ms": ms, "mpix_per_s": rows * cols / (ms * 1e-3) / 1e6})
+        if extra is not None:  # (--view_prior: the prior's sources, class counts and device time; the iterations run)
+            entry.update(extra)
         report.append(entry)
 
     pyr = None
@@ -229,7 +312,11 @@ def main(argv=None):
         from . import pyramid
         pyr = pyramid.ScanPyramid(dev, args.levels)  # the coarse planes of the whole scan, once
     t_batch0 = time.perf_counter()
+    order = None
     try:
+        if args.view_prior:
+            order = solve_with_view_prior(args, names, mine, P_all, dev, rows, cols, ap, dev_index, report, record)
+            mine = []
         for ref_name in mine:
             ref_idx = names.index(ref_name)
             cs, used, ap_view = plan_views(P_all, names, ref_idx, cols, rows, ap, args.cam_scale)
@@ -295,6 +382,9 @@ def main(argv=None):
                "in_flight": in_flight, "batch_seconds": t_batch,
                **({"levels": args.levels, "level_iterations": level_iterations, "pyramid_device_ms": pyr.device_ms}
                   if pyr is not None else {}),
+               **({"view_prior": args.view_prior, "prior_iterations": args.prior_iterations,
+                   "prior_min_views": args.prior_min_views, "prior_max_cost": args.prior_max_cost, "order": order}
+                  if order is not None else {}),
                "mpix_per_s_batch": n_done * rows * cols / max(t_batch, 1e-9) / 1e6,
                "views": report}
         if fused is not None:

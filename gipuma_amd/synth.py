@@ -372,3 +372,82 @@ def build_problem(cfg, ref_view=15, scene_seed=1234, solver_seed=1, device="cpu"
         gs = GlobalState([im.cpu().numpy() for im in imgs], cs, subset, ap, seed=solver_seed)
     info = dict(gt_depth=gt, view_ids=ids, cameras=cs, surface=surf, cfg=cfg, P_matrices=Ps, cam_scale=cam_scale)
     return gs, info
+
+
+class Scan:
+    """build_scan's result: one world surface seen by `n` calibrated views, each with its image and ground truth.
+    images[i]: (rows, cols) float32 0..255; P_matrices[i]: 3x4 (the fixture's, before cam_scale); gt_depth[i]: (rows, cols);
+    gt_norm4[i]: (rows, cols, 4) = (world normal towards camera i, depth), the public result form of a perfect solve."""
+
+    def problem(self, i, iterations=None):
+        """GlobalState with view i as the reference and every other view of the scan as its sources (in scan order),
+        the configuration's parameters and depth range"""
+        order = [i] + [j for j in range(len(self.images)) if j != i]
+        cs = get_camera_parameters([self.P_matrices[j] for j in order], cam_scale=self.cam_scale)
+        cfg = self.cfg
+        ap = AlgorithmParameters(iterations=cfg["iterations"] if iterations is None else int(iterations),
+                                 n_best=cfg["n_best"], depthMin=cfg["depth_min"], depthMax=cfg["depth_max"],
+                                 min_angle=cfg["min_angle"], max_angle=cfg["max_angle"], max_views=len(order),
+                                 gamma=self.gamma, cost_comb=self.cost_comb)
+        ap.set_blocksize(cfg["blocksize"])
+        return GlobalState([self.images[j] for j in order], cs, list(range(1, len(order))), ap, seed=self.solver_seed)
+
+
+def build_scan(cfg, ref_view=15, scene_seed=1234, solver_seed=1, device="cpu", gamma=10.0, cost_comb=abi.COMB_BEST_N,
+               scene="smooth", **overrides):
+    """The scan behind build_problem(cfg, ...) -- the reference view `ref_view` and its n_src sources, DTU geometry only
+    -- with EVERY view's ground truth: the same surface (defined in view 0's camera frame), the same images, and per
+    view the depth map and the world normals.  View 0's problem, scan.problem(0), is build_problem's."""
+    if isinstance(cfg, str):
+        cfg = dict(CONFIGS[cfg])
+    cfg = dict(cfg)
+    cfg.update(overrides)
+    if cfg["kind"] != "dtu":
+        raise ValueError("build_scan renders DTU-geometry configurations")
+    rows, cols, n_src = cfg["rows"], cfg["cols"], cfg["n_src"]
+    cam_scale = cfg.get("cam_scale", 1.0)
+    allP = dtu_projection_matrices()
+    order = [ref_view] + [k for k in sorted(allP) if k != ref_view]
+    cs_all = get_camera_parameters([allP[k] for k in order], cam_scale=cam_scale)
+    cand, _, _ = select_views(cs_all, cols, rows, cfg["min_angle"], cfg["max_angle"], max_views=10 ** 6)
+    if len(cand) < n_src:
+        raise ValueError("reference view %d has only %d neighbours in the cone" % (ref_view, len(cand)))
+    ids = [ref_view] + [order[cand[(i * len(cand)) // n_src]] for i in range(n_src)]
+    Ps = [allP[k] for k in ids]
+    z0, amp, wl, tilt = 600.0, 25.0, 160.0, (0.05, -0.03)
+    cs = get_camera_parameters(Ps, cam_scale=cam_scale)
+    footprint = z0 / cs.f
+    if scene == "steps":
+        surf = SteppedSurface(z0, amp, wl, tilt=tilt, pixel_footprint=footprint, seed=scene_seed, step=30.0,
+                              period=(300.0, 260.0), disc=(40.0, -30.0, 80.0, 90.0))
+    elif scene == "patchy":
+        surf = PatchySurface(z0, amp, wl, tilt=tilt, pixel_footprint=footprint, seed=scene_seed, band=(0.25, 40.0))
+    else:
+        surf = Surface(z0, amp, wl, tilt=tilt, pixel_footprint=footprint, seed=scene_seed)
+    s = Scan()
+    s.cfg, s.cam_scale, s.view_ids, s.P_matrices, s.surface, s.cameras = cfg, cam_scale, ids, Ps, surf, cs
+    s.gamma, s.cost_comb, s.solver_seed, s.scene = gamma, cost_comb, solver_seed, scene
+    s.images, s.gt_depth, s.gt_norm4 = [], [], []
+    v, u = np.mgrid[0:rows, 0:cols].astype(np.float64)
+    pix = np.stack([u, v, np.ones_like(u)], -1)
+    R0 = cs.R_orig[0]
+    for i in range(cs.n):
+        if scene in ("patchy", "steps"):
+            img, depth = render_march(surf, cs.K[i], cs.R[i], cs.t[i], rows, cols, device=device,
+                                      zspan=(z0 * 0.63, z0 * 1.27), noise_sigma=1.0 if scene == "patchy" else 2.0,
+                                      noise_seed=scene_seed + i)
+        else:
+            img, depth = render(surf, cs.K[i], cs.R[i], cs.t[i], rows, cols, device=device)
+        d = depth.cpu().numpy().astype(np.float64)
+        # the surface point of every pixel in view 0's frame, its normal (-h_x, -h_y, 1) turned towards camera i, and
+        # that normal in the world: n_world = R0^T n
+        Xr = (d[..., None] * (pix @ np.linalg.inv(cs.K[i]).T) - cs.t[i]) @ cs.R[i]
+        hx, hy = surf.grad(torch.from_numpy(Xr[..., 0]), torch.from_numpy(Xr[..., 1]))
+        nr = np.stack([-hx.numpy(), -hy.numpy(), np.ones_like(u)], -1)
+        nr /= np.linalg.norm(nr, axis=-1, keepdims=True)
+        centre = -cs.R[i].T @ cs.t[i]
+        nr[((centre - Xr) * nr).sum(-1) < 0] *= -1.0
+        s.images.append(img.cpu().numpy())
+        s.gt_depth.append(d.astype(np.float32))
+        s.gt_norm4.append(np.concatenate([nr @ R0, d[..., None]], axis=-1).astype(np.float32))
+    return s

@@ -323,6 +323,52 @@ int gipuma_hip_fusion_points(const gipuma_hip_fusion *f, void *vertices, int64_t
 int gipuma_hip_fusion_used(const gipuma_hip_fusion *f, uint8_t *masks);
 int gipuma_hip_fusion_free(gipuma_hip_fusion *f);
 
+/* ---- the cross-view prior: solved (n_world, depth) maps of other cameras -> a start for a new reference view ----
+ * Carries the result planes of n_sources already-solved views (1 .. GIPUMA_HIP_MAX_VIEWS, all rows x cols) into the
+ * target camera, in the public result form gipuma_hip_seed_planes / gipuma_hip_solve_seeded take at shift 0.  The
+ * reference has nothing like it; the contract is this project's own.  Float32 without contraction, valid(z) as in the
+ * fusion (finite, > 0, inside depth_min / depth_max where those are > 0):
+ *   splat:   every source pixel (x, y) of source k with valid depth z, a finite normal n with n.n > 0 and -- when cost
+ *            planes are given -- cost <= max_cost is back-projected, X = c_k + z (bp_k (x, y, 1)), and projected with the
+ *            target's P: h = P_t (X, 1).  It is kept when h_2 > 0 and valid(h_2), its nearest pixel
+ *            q = floor(h_0 / h_2 + 0.5, h_1 / h_2 + 0.5) is inside the frame and its plane faces the target camera,
+ *            n . (bp_t (q, 1)) < 0.  Then  zbuf[q] = min(zbuf[q], bits(h_2) << 32 | k rows cols + y cols + x)  as one
+ *            64-bit unsigned atomic minimum: the nearest surface wins, a tie goes to the lower source ordinal, then to
+ *            the lower source pixel -- whatever the launch geometry and the order the workgroups run in.
+ *   resolve: a target pixel takes its own key (class `direct`) or, when it has none and fill = 1, the smallest key of
+ *            its 8 neighbours inside the frame (class `filled`).  The winner's plane is intersected with the pixel's OWN
+ *            ray r = bp_t (x, y, 1):  zc = n . (X - c_t) / n . r  (the depth a nearest-pixel splat loses 2-3e-4 of).
+ *            zc is used when it is valid and the ray is not grazing, (n . r)^2 > grazing_cos^2 (n . n)(r . r); otherwise
+ *            a direct pixel keeps the splatted depth h_2 and a filled one becomes empty.  prior = (n, depth); an
+ *            `empty` pixel is (0, 0, 0, 0), which gipuma_hip_seed_planes answers with the random plane of
+ *            gipuma_hip_init_planes.
+ * target: bp, c and P are read (norm4, gray, fb are not); sources: norm4, bp and c.  The constants are those of
+ * gipuma_amd/fusion.py view_constants.  costs: NULL, or a host array of n_sources device planes of rows * cols floats.
+ * A frame may have at most 2^30 pixels (pixel indices are int; more is GIPUMA_HIP_ERR_ARG, as in the fusion); within
+ * that, n_sources * rows * cols >= 2^32 is refused with GIPUMA_HIP_ERR_UNSUPPORTED (the key's low word). */
+typedef struct gipuma_hip_prior_desc {
+    uint32_t abi_version;                  /* GIPUMA_HIP_ABI_VERSION */
+    int32_t rows, cols;                    /* of every view */
+    gipuma_hip_fusion_view target;         /* the new reference camera */
+    int32_t n_sources;                     /* 1 .. GIPUMA_HIP_MAX_VIEWS */
+    const gipuma_hip_fusion_view *sources; /* host array of n_sources entries, device planes */
+    const float *const *costs;             /* NULL, or host array of n_sources device cost planes */
+    float max_cost;                        /* with costs: source pixels with cost > max_cost are left out */
+    float depth_min, depth_max;            /* depths outside are invalid; <= 0: no bound */
+    float grazing_cos;                     /* 0 .. 1; f32(cos(80 degrees)) computed in double is the usual value */
+    int32_t fill;                          /* 1: empty pixels look at their 8 neighbours; 0: they stay empty */
+    int32_t device_id;                     /* HIP device ordinal */
+    void *stream;                          /* hipStream_t to enqueue on; NULL = the null stream, complete on return */
+} gipuma_hip_prior_desc;
+
+/* Writes rows * cols float4 to the caller's device buffer prior_dev.  Enqueues on desc->stream and synchronises only
+ * when `counts` (the number of direct, filled and empty pixels) or `device_ms` (memset + both kernels, HIP events) is
+ * asked for; either may be NULL.  The source planes must be complete on that stream's terms when the call is made.
+ * Scratch: the 8-byte-per-pixel key plane is cached per device (grown when a larger frame comes, kept until the process
+ * ends) and shared by every call on that device, so two calls on one device must not run side by side: keep them on
+ * one stream, or let the first finish. */
+int gipuma_hip_prior_from_views(const gipuma_hip_prior_desc *desc, float *prior_dev, int64_t counts[3], float *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
