@@ -75,11 +75,31 @@ FUSION_MAX_VIEWS = 512  # GIPUMA_HIP_FUSION_MAX_VIEWS (MAX_IMAGES, config.h:2)
 
 
 class FusionView(C.Structure):
-    """gipuma_hip_fusion_view: one view's device planes and float32 camera constants (gipuma_amd.fusion.view_constants)"""
+    """gipuma_hip_fusion_view: one view's device planes and float32 camera constants (gipuma_amd.cameras.view_constants)"""
     _fields_ = [
         ("norm4", C.c_void_p), ("gray", C.c_void_p), ("bp", C.c_float * 9), ("c", C.c_float * 3),
         ("P", C.c_float * 12), ("fb", C.c_float),
     ]
+
+
+def fill_view(v, k, norm4=None, gray=None):
+    """fills the FusionView `v` from k = cameras.view_constants(P, cam_scale) and the device addresses of its planes"""
+    v.norm4, v.gray = norm4, gray
+    v.bp[:] = [float(x) for x in k["bp"].reshape(-1)]
+    v.c[:] = [float(x) for x in k["c"]]
+    v.P[:] = [float(x) for x in k["P"].reshape(-1)]
+    v.fb = float(k["fb"])
+
+
+def device_plane(a, device, keep):
+    """The device address of the float32 plane `a` on `device`: a device tensor is passed through (no copy), a host array
+    uploaded.  `keep`: the caller's list that holds the tensor alive for as long as the library may read it."""
+    import numpy as np
+    import torch
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    t = t.to(device=device, dtype=torch.float32).contiguous()
+    keep.append(t)
+    return t.data_ptr()
 
 
 class FusionDesc(C.Structure):

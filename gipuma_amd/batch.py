@@ -37,7 +37,6 @@ Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
 """
 import argparse
 import collections
-import ctypes as C
 import json
 import os
 import sys
@@ -128,26 +127,122 @@ def plan_views(P_all, names, ref_idx, cols, rows, ap, cam_scale=1.0):
 PRIOR_ITERATIONS = 1
 
 
-def solve_with_view_prior(args, names, mine, P_all, dev, rows, cols, ap, dev_index, report, record):
+class Scan:
+    """What every solve strategy works on: the whole scan resident in the HBM of one device (loaded here, once), the
+    parameters, and what the run collects (the report's entries; with --fuse the solved maps)."""
+
+    def __init__(self, args, dev_index):
+        import torch
+        self.args = args
+        self.names = sorted(n for n in os.listdir(args.images_folder) if n.lower().endswith(IMAGE_EXTENSIONS))
+        if len(self.names) < 2:
+            raise SystemExit("need at least 2 images (png / jpg / pgm / ppm) in %s" % args.images_folder)
+        self.P_all = [read_p_file(os.path.join(args.p_folder, n + ".P")) for n in self.names]
+        t0 = time.perf_counter()
+        self.dev = [torch.from_numpy(read_image(os.path.join(args.images_folder, n))).to("cuda:%d" % dev_index)
+                    for n in self.names]
+        torch.cuda.synchronize()
+        self.load_seconds = time.perf_counter() - t0
+        self.rows, self.cols = (int(n) for n in self.dev[0].shape)
+        self.ap = AlgorithmParameters(iterations=args.iterations, n_best=args.n_best, gamma=args.cost_gamma,
+                                      depthMin=args.depth_min, depthMax=args.depth_max, min_angle=args.min_angle,
+                                      max_angle=args.max_angle, max_views=args.max_views)
+        self.ap.set_blocksize(args.blocksize)
+        self.flavour = dict(fast=args.mode == "fast", literal=args.mode == "literal")  # of every Session (--mode)
+        self.report = []
+        self.solved = {}  # reference name -> norm4 (host), for --fuse
+
+    def plans(self, mine):
+        """(name, *plan_views) of every view of `mine` with a source inside the angle cone; the others go to the report"""
+        for ref_name in mine:
+            plan = plan_views(self.P_all, self.names, self.names.index(ref_name), self.cols, self.rows, self.ap, self.args.cam_scale)
+            if len(plan[1]) < 2:
+                self.report.append({"ref": ref_name, "skipped": "no source view inside the angle cone"})
+            else:
+                yield (ref_name,) + plan
+
+    def record(self, ref_name, used, tw0, t, n4, cost, levels=None, extra=None):
+        """writes the dumps of one solved view and its entry of the report"""
+        wall_ms = (time.perf_counter() - tw0) * 1e3  # session set-up + solve (+ what ran beside it) + download
+        folder = os.path.join(self.args.output_folder, os.path.splitext(ref_name)[0])
+        os.makedirs(folder, exist_ok=True)
+        dmb.write_dmb(os.path.join(folder, "disp.dmb"), n4[..., 3])
+        dmb.write_dmb(os.path.join(folder, "normals.dmb"), n4[..., :3])
+        dmb.write_dmb(os.path.join(folder, "cost.dmb"), cost)
+        if self.args.fuse:
+            self.solved[ref_name] = n4
+        npix = self.rows * self.cols
+        entry = {"ref": ref_name, "sources": [self.names[i] for i in used[1:]], "wall_ms": wall_ms,
+                 "mpix_per_s_wall": npix / (wall_ms * 1e-3) / 1e6}
+        if t is not None:  # one view at a time: the device time is that view's alone
+            entry.update({"device_ms": t.ms_total, "mpix_per_s": npix / (t.ms_total * 1e-3) / 1e6})
+        if levels is not None:  # (--levels > 1, one view at a time: device times per level, coarsest first)
+            ms = sum(lv["ms_total"] for lv in levels)
+            entry.update({"levels": levels, "device_ms": ms, "mpix_per_s": npix / (ms * 1e-3) / 1e6})
+        if extra is not None:  # (--view_prior: the prior's sources, class counts and device time; the iterations run)
+            entry.update(extra)
+        self.report.append(entry)
+
+
+def solve_plain(scan, mine, in_flight):
+    """The views of `mine` in order, `in_flight` of them at a time: one session and stream each, the solves enqueued
+    asynchronously (in_flight 1: one at a time, with per-view device times)."""
+    pending = collections.deque()  # (session, reference name, used, start time, timing or None)
+
+    def retire():
+        s, ref_name, used, tw0, t = pending.popleft()
+        try:
+            n4, cost = s.get_state()  # waits for the session's stream
+        finally:
+            s.close()
+        scan.record(ref_name, used, tw0, t, n4, cost)
+
+    try:
+        for ref_name, cs, used, ap_view in scan.plans(mine):
+            gs = GlobalState.on_resident_planes(scan.dev, used, cs, ap_view, seed=scan.args.seed)
+            tw0 = time.perf_counter()
+            s = Session(gs, **scan.flavour)
+            try:
+                t = s.solve(timing=in_flight == 1)  # (untimed: asynchronous, returns once the launches are enqueued)
+            except Exception:
+                s.close()
+                raise
+            pending.append((s, ref_name, used, tw0, t if in_flight == 1 else None))
+            while len(pending) >= in_flight:
+                retire()
+        while pending:
+            retire()
+    finally:  # (an error above: do not leave sessions of this batch behind)
+        for leftover in pending:
+            leftover[0].close()
+
+
+def solve_levels(scan, mine, pyr, level_iterations, timing):
+    """--levels: the views of `mine` one at a time, each coarse-to-fine over the scan's pyramid.  View selection and the
+    depth range are decided by plan_views, on the finest level; every level reuses them."""
+    from . import pyramid
+    for ref_name, _, used, ap_view in scan.plans(mine):
+        tw0 = time.perf_counter()
+        n4, cost, times = pyramid.solve_view(pyr, scan.P_all, used, ap_view, level_iterations, seed=scan.args.seed,
+                                             mode=scan.args.mode, cam_scale=scan.args.cam_scale, timing=timing)
+        scan.record(ref_name, used, tw0, None, n4, cost, times if timing else None)
+
+
+def solve_with_view_prior(scan, mine):
     """--view_prior: the views of `mine` in gipuma_amd.prior.greedy_order, one at a time.  A view with at least
     --prior_min_views solved sources starts from the prior of the first --view_prior of them (in selection order) and runs
     --prior_iterations iterations; any other view runs the plain solve.  Returns the order."""
     import torch
     from . import prior as view_prior
-    plans = {}
-    for ref_name in mine:
-        cs, used, ap_view = plan_views(P_all, names, names.index(ref_name), cols, rows, ap, args.cam_scale)
-        if len(used) < 2:
-            report.append({"ref": ref_name, "skipped": "no source view inside the angle cone"})
-            continue
-        plans[ref_name] = (cs, used, ap_view)
-    order = view_prior.greedy_order([n for n in mine if n in plans],
-                                    {n: [names[i] for i in plans[n][1][1:]] for n in plans})
+    args, names, P_all = scan.args, scan.names, scan.P_all
+    device = scan.dev[0].device
+    planned = list(scan.plans(mine))  # (the views without a source are in the report by now, ahead of the solved ones)
+    plans = {p[0]: p[1:] for p in planned}
+    order = view_prior.greedy_order([p[0] for p in planned], {n: [names[i] for i in plans[n][1][1:]] for n in plans})
     kept = {}  # reference name -> (norm4, cost or None) on the device, for the views solved after it
     for ref_name in order:
         cs, used, ap_view = plans[ref_name]
-        sources = [names[i] for i in used[1:]]
-        have = [n for n in sources if n in kept][:args.view_prior]
+        have = [names[i] for i in used[1:] if names[i] in kept][:args.view_prior]
         tw0 = time.perf_counter()
         start, pinfo = None, None
         if len(have) >= args.prior_min_views:
@@ -155,27 +250,23 @@ def solve_with_view_prior(args, names, mine, P_all, dev, rows, cols, ap, dev_ind
             start, pinfo = view_prior.prior_from_views(
                 P_all[used[0]], [kept[n][0] for n in have], [P_all[names.index(n)] for n in have], args.cam_scale,
                 ap_view.depthMin, ap_view.depthMax, costs=[kept[n][1] for n in have] if with_cost else None,
-                max_cost=args.prior_max_cost, return_info=True, device_id=dev_index)
+                max_cost=args.prior_max_cost, return_info=True, device_id=device.index)
             ap_view.iterations = args.prior_iterations
-        imgs = [dev[i] for i in used]
-        gs = GlobalState(imgs, cs, list(range(1, len(used))), ap_view, seed=args.seed,
-                         device_ptrs=[t.data_ptr() for t in imgs], rows=rows, cols=cols, device_id=dev_index,
-                         flags=abi.FLAG_CACHE_IMAGES)
-        with Session(gs, fast=args.mode == "fast", literal=args.mode == "literal") as s:
+        with Session(GlobalState.on_resident_planes(scan.dev, used, cs, ap_view, seed=args.seed), **scan.flavour) as s:
             t = s.solve(timing=True) if start is None else s.solve_seeded(start, 0, timing=True)
             n4, cost = s.get_state()
         # (kept in HBM for the views solved later: uploaded again from the host copy the dumps need anyway, 31 MB per
         #  1600x1200 view -- a device-to-device copy out of the session would save that upload)
-        kept[ref_name] = (torch.from_numpy(n4).to("cuda:%d" % dev_index),
-                          torch.from_numpy(cost).to("cuda:%d" % dev_index) if args.prior_max_cost is not None else None)
+        kept[ref_name] = (torch.from_numpy(n4).to(device),
+                          torch.from_numpy(cost).to(device) if args.prior_max_cost is not None else None)
         torch.cuda.synchronize()
-        extra = {"iterations": int(ap_view.iterations),
-                 "prior": None if pinfo is None else dict(sources=have, **pinfo)}
-        record(ref_name, sources, tw0, t, n4, cost, extra=extra)
+        scan.record(ref_name, used, tw0, t, n4, cost,
+                    extra={"iterations": int(ap_view.iterations), "prior": None if pinfo is None else dict(sources=have, **pinfo)})
     return order
 
 
-def main(argv=None):
+def parse_args(argv):
+    """the command line, checked; args.level_iterations comes back as the list of counts, coarsest first"""
     pa = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     pa.add_argument("--images-folder", required=True)
     pa.add_argument("--p-folder", required=True)
@@ -228,9 +319,9 @@ def main(argv=None):
         setattr(args, k, float(np.float32(getattr(args, k))))
     if args.levels < 1:
         raise SystemExit("--levels must be >= 1")
-    level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
+    args.level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
         [args.iterations] + [2] * (args.levels - 1)
-    if args.levels > 1 and len(level_iterations) != args.levels:
+    if args.levels > 1 and len(args.level_iterations) != args.levels:
         raise SystemExit("--level_iterations needs %d values, coarsest first" % args.levels)
     if args.view_prior < 0 or args.view_prior > abi.MAX_VIEWS:
         raise SystemExit("--view_prior must be 0..%d" % abi.MAX_VIEWS)
@@ -245,7 +336,44 @@ def main(argv=None):
     if args.fuse and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--fuse works within one process (there is no exchange of results between ranks): run "
                          "`python -m gipuma_amd.fusion --input-folder %s ...` once every rank is done" % args.output_folder)
+    return args
 
+
+def fuse_solved(scan):
+    """--fuse: the views solved in this run, from memory, into <output-folder>/fused.ply; returns the report's entry"""
+    from . import fusion
+    args, names = scan.args, scan.names
+    # the views solved here, in the scan's order (that of the fusion CLI on the dumps); skipped ones are left out
+    fused_views = [n for n in names if n in scan.solved]
+    if len(fused_views) < 2:
+        raise SystemExit("--fuse needs at least 2 solved views, this run solved %d" % len(fused_views))
+    points, info = fusion.fuse([scan.solved[n] for n in fused_views], [scan.dev[names.index(n)] for n in fused_views],
+                               [scan.P_all[names.index(n)] for n in fused_views], args.cam_scale, args.disp_thresh,
+                               args.normal_thresh, args.num_consistent, args.depth_min, args.depth_max,
+                               device_id=scan.dev[0].device.index, return_info=True)
+    dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
+    return {"points": int(len(points)), "device_ms": info["device_ms"],
+            "views": [{"name": n, "emitted": int(c)} for n, c in zip(fused_views, info["per_view"])]}
+
+
+def write_report(scan, head, pyr, order, fused):
+    """batch_rank<rank>.json: `head`, the options of the strategy that ran, the throughput and the per-view entries"""
+    args, t_batch = scan.args, head["batch_seconds"]
+    n_done = sum(1 for r in scan.report if "skipped" not in r)
+    out = {**head,
+           **({"levels": args.levels, "level_iterations": args.level_iterations, "pyramid_device_ms": pyr.device_ms}
+              if pyr is not None else {}),
+           **({"view_prior": args.view_prior, "prior_iterations": args.prior_iterations,
+               "prior_min_views": args.prior_min_views, "prior_max_cost": args.prior_max_cost, "order": order}
+              if args.view_prior else {}),
+           "mpix_per_s_batch": n_done * scan.rows * scan.cols / max(t_batch, 1e-9) / 1e6,
+           "views": scan.report, **({"fusion": fused} if fused is not None else {})}
+    with open(os.path.join(args.output_folder, "batch_rank%d.json" % head["rank"]), "w") as f:
+        json.dump(out, f, indent=1)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     import torch
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -254,143 +382,35 @@ def main(argv=None):
         raise abi.GipumaHipError("gipuma_amd.batch needs a GPU; there is no CPU fallback")
     dev_index = local_rank % torch.cuda.device_count()
     torch.cuda.set_device(dev_index)
-
-    names = sorted(n for n in os.listdir(args.images_folder) if n.lower().endswith(IMAGE_EXTENSIONS))
-    if len(names) < 2:
-        raise SystemExit("need at least 2 images (png / jpg / pgm / ppm) in %s" % args.images_folder)
-    P_all = [read_p_file(os.path.join(args.p_folder, n + ".P")) for n in names]
-    # the whole scan resident in HBM, once
-    t0 = time.perf_counter()
-    host = [read_image(os.path.join(args.images_folder, n)) for n in names]
-    rows, cols = host[0].shape
-    dev = [torch.from_numpy(im).to("cuda:%d" % dev_index) for im in host]
-    torch.cuda.synchronize()
-    t_load = time.perf_counter() - t0
-
-    refs = names if args.views == "all" else [v for v in args.views.split(",") if v]
+    scan = Scan(args, dev_index)
+    refs = scan.names if args.views == "all" else [v for v in args.views.split(",") if v]
     mine = views_for_rank(refs, rank, world) if len(refs) >= world else refs[rank:rank + 1]
-    ap = AlgorithmParameters(iterations=args.iterations, n_best=args.n_best, gamma=args.cost_gamma,
-                             depthMin=args.depth_min, depthMax=args.depth_max, min_angle=args.min_angle,
-                             max_angle=args.max_angle, max_views=args.max_views)
-    ap.set_blocksize(args.blocksize)
     os.makedirs(args.output_folder, exist_ok=True)
-    report = []
     in_flight = max(1, args.in_flight)
-    pending = collections.deque()  # (session, reference name, source names, start time, timing or None)
-    solved = {}  # reference name -> norm4 (host), for --fuse
-
-    def retire():
-        s, ref_name, sources, tw0, t = pending.popleft()
-        try:
-            n4, cost = s.get_state()  # waits for the session's stream
-        finally:
-            s.close()
-        record(ref_name, sources, tw0, t, n4, cost)
-
-    def record(ref_name, sources, tw0, t, n4, cost, levels=None, extra=None):
-        wall_ms = (time.perf_counter() - tw0) * 1e3  # session set-up + solve (+ what ran beside it) + download
-        folder = os.path.join(args.output_folder, os.path.splitext(ref_name)[0])
-        os.makedirs(folder, exist_ok=True)
-        dmb.write_dmb(os.path.join(folder, "disp.dmb"), n4[..., 3])
-        dmb.write_dmb(os.path.join(folder, "normals.dmb"), n4[..., :3])
-        dmb.write_dmb(os.path.join(folder, "cost.dmb"), cost)
-        if args.fuse:
-            solved[ref_name] = n4
-        entry = {"ref": ref_name, "sources": sources, "wall_ms": wall_ms,
-                 "mpix_per_s_wall": rows * cols / (wall_ms * 1e-3) / 1e6}
-        if t is not None:  # one view at a time: the device time is that view's alone
-            entry.update({"device_ms": t.ms_total, "mpix_per_s": rows * cols / (t.ms_total * 1e-3) / 1e6})
-        if levels is not None:  # (--levels > 1, one view at a time: device times per level, coarsest first)
-            ms = sum(lv["ms_total"] for lv in levels)
-            entry.update({"levels": levels, "device_ms": ms, "mpix_per_s": rows * cols / (ms * 1e-3) / 1e6})
-        if extra is not None:  # (--view_prior: the prior's sources, class counts and device time; the iterations run)
-            entry.update(extra)
-        report.append(entry)
-
     pyr = None
     if args.levels > 1:
         from . import pyramid
-        pyr = pyramid.ScanPyramid(dev, args.levels)  # the coarse planes of the whole scan, once
+        pyr = pyramid.ScanPyramid(scan.dev, args.levels)  # the coarse planes of the whole scan, once
     t_batch0 = time.perf_counter()
-    order = None
+    order = None  # (--view_prior: the order the views were solved in)
     try:
         if args.view_prior:
-            order = solve_with_view_prior(args, names, mine, P_all, dev, rows, cols, ap, dev_index, report, record)
-            mine = []
-        for ref_name in mine:
-            ref_idx = names.index(ref_name)
-            cs, used, ap_view = plan_views(P_all, names, ref_idx, cols, rows, ap, args.cam_scale)
-            if len(used) < 2:
-                report.append({"ref": ref_name, "skipped": "no source view inside the angle cone"})
-                continue
-            if pyr is not None:
-                # view selection and the depth range were decided above, on the finest level; every level reuses them
-                tw0 = time.perf_counter()
-                n4, cost, times = pyramid.solve_view(pyr, P_all, used, ap_view, level_iterations, seed=args.seed,
-                                                     mode=args.mode, cam_scale=args.cam_scale, timing=in_flight == 1)
-                record(ref_name, [names[i] for i in used[1:]], tw0, None, n4, cost, times if in_flight == 1 else None)
-                continue
-            imgs = [dev[i] for i in used]
-            # the scan's planes stay put for the whole batch: what the library derives from them (8-bit
-            # check, window-packed copies) is made once per image, not once per reference view that uses it
-            gs = GlobalState(imgs, cs, list(range(1, len(used))), ap_view, seed=args.seed,
-                             device_ptrs=[t.data_ptr() for t in imgs], rows=rows, cols=cols, device_id=dev_index,
-                             flags=abi.FLAG_CACHE_IMAGES)
-            tw0 = time.perf_counter()
-            s = Session(gs, fast=args.mode == "fast", literal=args.mode == "literal")
-            try:
-                if in_flight == 1:
-                    t = s.solve(timing=True)
-                else:
-                    t = None
-                    s.solve(timing=False)  # asynchronous: returns once the launches are enqueued
-            except Exception:
-                s.close()
-                raise
-            pending.append((s, ref_name, [names[i] for i in used[1:]], tw0, t))
-            while len(pending) >= in_flight:
-                retire()
-        while pending:
-            retire()
-    finally:  # (an error above: do not leave sessions of this batch behind)
-        for leftover in pending:
-            leftover[0].close()
-        pending.clear()
+            order = solve_with_view_prior(scan, mine)
+        elif pyr is not None:
+            solve_levels(scan, mine, pyr, args.level_iterations, timing=in_flight == 1)
+        else:
+            solve_plain(scan, mine, in_flight)
+    finally:
         if pyr is not None:
             pyr.close()  # (clears the image cache before the coarse planes are released)
-        # ... nor the image cache: its entries are keyed by the device addresses of `dev`'s tensors, which
-        # torch hands out again once they are freed (the library refuses while a session still uses them)
+        # an error above must not leave the image cache behind: its entries are keyed by the device addresses of the
+        # scan's tensors, which torch hands out again once they are freed (the library refuses while a session still
+        # uses them)
         abi.load_library().gipuma_hip_cache_clear()
     t_batch = time.perf_counter() - t_batch0
-    fused = None
-    if args.fuse:
-        # the views solved here, in the scan's order (that of the fusion CLI on the dumps); skipped ones are left out
-        order = [n for n in names if n in solved]
-        if len(order) < 2:
-            raise SystemExit("--fuse needs at least 2 solved views, this run solved %d" % len(order))
-        from . import fusion
-        points, info = fusion.fuse([solved[n] for n in order], [dev[names.index(n)] for n in order],
-                                   [P_all[names.index(n)] for n in order], args.cam_scale, args.disp_thresh,
-                                   args.normal_thresh, args.num_consistent, args.depth_min, args.depth_max,
-                                   device_id=dev_index, return_info=True)
-        dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
-        fused = {"points": int(len(points)), "device_ms": info["device_ms"],
-                 "views": [{"name": n, "emitted": int(c)} for n, c in zip(order, info["per_view"])]}
-    with open(os.path.join(args.output_folder, "batch_rank%d.json" % rank), "w") as f:
-        n_done = sum(1 for r in report if "skipped" not in r)
-        out = {"rank": rank, "world": world, "device": dev_index, "load_seconds": t_load,
-               "in_flight": in_flight, "batch_seconds": t_batch,
-               **({"levels": args.levels, "level_iterations": level_iterations, "pyramid_device_ms": pyr.device_ms}
-                  if pyr is not None else {}),
-               **({"view_prior": args.view_prior, "prior_iterations": args.prior_iterations,
-                   "prior_min_views": args.prior_min_views, "prior_max_cost": args.prior_max_cost, "order": order}
-                  if order is not None else {}),
-               "mpix_per_s_batch": n_done * rows * cols / max(t_batch, 1e-9) / 1e6,
-               "views": report}
-        if fused is not None:
-            out["fusion"] = fused
-        json.dump(out, f, indent=1)
-    print("rank %d/%d: %d reference views on cuda:%d" % (rank, world, len(report), dev_index))
+    write_report(scan, {"rank": rank, "world": world, "device": dev_index, "load_seconds": scan.load_seconds,
+                        "in_flight": in_flight, "batch_seconds": t_batch}, pyr, order, fuse_solved(scan) if args.fuse else None)
+    print("rank %d/%d: %d reference views on cuda:%d" % (rank, world, len(scan.report), dev_index))
     return 0
 
 

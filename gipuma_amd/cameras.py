@@ -81,6 +81,27 @@ def scale_k(K, s):
     return K
 
 
+BASELINE = 0.54  # cameraGeometryUtils.h:305
+
+
+def view_constants(P, cam_scale=1.0):
+    """The float32 constants of one view (gipuma_hip_fusion_view, abi.fill_view), the only place they are made: from
+    P = K [R | -R C] (not re-centred), K scaled by cam_scale, in float64, rounded once.  bp = R^T K^-1, c = C,
+    P = [K R | -K R C], fb = f32(f32(K[0][0]) * 0.54f)."""
+    K, R, Cc = decompose_projection(P)
+    K = scale_k(K, cam_scale)
+    KR = K @ R
+    f32 = np.float32
+    return dict(bp=(R.T @ np.linalg.inv(K)).astype(f32), c=Cc.astype(f32),
+                P=np.concatenate([KR, (-KR @ Cc)[:, None]], axis=1).astype(f32),
+                fb=f32(f32(K[0, 0]) * f32(BASELINE)))
+
+
+def cos_f32(degrees):
+    """f32(cos(degrees * pi / 180)), computed in double: how a threshold given as an angle reaches the library"""
+    return np.float32(math.cos(float(degrees) * math.pi / 180.0))
+
+
 def camera_centre(P):
     """getCameraCenter, cameraGeometryUtils.h:22-49 (signed 3x3 minors), normalised."""
     c = np.empty(4)
@@ -160,7 +181,7 @@ def get_camera_parameters(P_list, cam_scale=1.0):
         cam.fy = K0[1, 1]
         cam.f = K0[0, 0]
         cam.alpha = float(np.float32(K0[0, 0]) / np.float32(K0[1, 1]))
-        cam.baseline = 0.54                                  # :305
+        cam.baseline = BASELINE                                # :305
         cam.depth_min = 2.0                                  # camera.h:34
         cam.depth_max = 20.0                                 # camera.h:38
     return cs

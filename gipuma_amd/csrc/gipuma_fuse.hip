@@ -19,33 +19,21 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <new>
-#include <string>
 #include <vector>
 
-#include "../../include/gipuma_hip.h"
+#include "pm_host.h"
+#include "pm_view.h"
 
-// the library's last-error text (gipuma_hip.hip; hidden, not part of the C-ABI)
-extern "C" __attribute__((visibility("hidden"))) void gipuma_set_last_error(const char *text);
+using pm_host::fail;
 
 namespace fuse {
 
 constexpr int kBlock = 256;  // pixels per workgroup of evaluate / scatter: 4 wavefronts
 constexpr int kScan = 1024;  // threads of the scan workgroup
 
-// Loads through the global address space: a pointer loaded from memory is a generic one to the compiler, and its accesses
-// would be flat_* (pm_core.h DevPtr, tests/test_isa_waits.py).
-template <class T>
-__device__ __forceinline__ T load_global(uint64_t base, int idx)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return ((const __attribute__((address_space(1))) T *)base)[idx];
-#else
-    return ((const T *)base)[idx];
-#endif
-}
+using namespace pm_view;  // the contract's operation order: load_global, valid_depth, backproject, project, dot
 
 struct View {  // gipuma_hip_fusion_view with the planes as integers (device table, scalar loads)
     uint64_t norm4, gray;
@@ -57,28 +45,21 @@ struct Params {
     float disp_thresh, cos_t, depth_min, depth_max;
 };
 
-__device__ __forceinline__ bool valid(float z, const Params &p)
-{
-    return isfinite(z) && z > 0.f && (p.depth_min <= 0.f || z >= p.depth_min) && (p.depth_max <= 0.f || z <= p.depth_max);
-}
-
 // The consistency test of X (normal n) against view v.  On success q = the partner's pixel index, (qx, qy) its
 // coordinates and m its (n', z').
-__device__ __forceinline__ bool consistent(const View &v, const Params &p, float X0, float X1, float X2, float nx, float ny,
-                                           float nz, int &q, float &qx, float &qy, float4 &m)
+__device__ __forceinline__ bool consistent(const View &v, const Params &p, const Vec3 &X, const Vec3 &n, int &q, float &qx,
+                                           float &qy, float4 &m)
 {
-    const float h0 = ((v.P[0] * X0 + v.P[1] * X1) + v.P[2] * X2) + v.P[3];
-    const float h1 = ((v.P[4] * X0 + v.P[5] * X1) + v.P[6] * X2) + v.P[7];
-    const float h2 = ((v.P[8] * X0 + v.P[9] * X1) + v.P[10] * X2) + v.P[11];
-    if (!(h2 > 0.f)) return false;
-    qx = floorf(h0 / h2 + 0.5f);
-    qy = floorf(h1 / h2 + 0.5f);
+    const Vec3 h = project(v, X);
+    if (!(h.z > 0.f)) return false;
+    qx = floorf(h.x / h.z + 0.5f);
+    qy = floorf(h.y / h.z + 0.5f);
     if (!(qx >= 0.f && qx <= (float)(p.cols - 1) && qy >= 0.f && qy <= (float)(p.rows - 1))) return false;
     q = (int)qy * p.cols + (int)qx;
     m = load_global<float4>(v.norm4, q);
-    if (!valid(m.w, p)) return false;
-    if (!(fabsf(v.fb / h2 - v.fb / m.w) < p.disp_thresh)) return false;
-    return ((nx * m.x + ny * m.y) + nz * m.z) > p.cos_t;
+    if (!valid_depth(m.w, p)) return false;
+    if (!(fabsf(v.fb / h.z - v.fb / m.w) < p.disp_thresh)) return false;
+    return dot(n, Vec3{m.x, m.y, m.z}) > p.cos_t;
 }
 
 __global__ __launch_bounds__(kBlock) void evaluate_kernel(const View *__restrict__ views, Params p, int i,
@@ -93,12 +74,10 @@ __global__ __launch_bounds__(kBlock) void evaluate_kernel(const View *__restrict
         const View &vi = views[i];
         const float4 s = load_global<float4>(vi.norm4, pix);
         const float z = s.w;
-        if (valid(z, p) && !used[(size_t)i * npix + pix]) {
-            const float xf = (float)(pix % p.cols), yf = (float)(pix / p.cols);
-            const float X0 = vi.c[0] + z * ((vi.bp[0] * xf + vi.bp[1] * yf) + vi.bp[2]);
-            const float X1 = vi.c[1] + z * ((vi.bp[3] * xf + vi.bp[4] * yf) + vi.bp[5]);
-            const float X2 = vi.c[2] + z * ((vi.bp[6] * xf + vi.bp[7] * yf) + vi.bp[8]);
-            float S0 = X0, S1 = X1, S2 = X2, N0 = s.x, N1 = s.y, N2 = s.z;
+        if (valid_depth(z, p) && !used[(size_t)i * npix + pix]) {
+            const Vec3 X = backproject(vi, z, (float)(pix % p.cols), (float)(pix / p.cols));
+            const Vec3 n = {s.x, s.y, s.z};
+            float S0 = X.x, S1 = X.y, S2 = X.z, N0 = s.x, N1 = s.y, N2 = s.z;
             float SG = vi.gray ? load_global<float>(vi.gray, pix) : 0.f;
             int count = 0;
             for (int j = 0; j < p.n_views; ++j) {  // wave-uniform
@@ -107,11 +86,12 @@ __global__ __launch_bounds__(kBlock) void evaluate_kernel(const View *__restrict
                 int q;
                 float qx, qy;
                 float4 m;
-                if (!consistent(vj, p, X0, X1, X2, s.x, s.y, s.z, q, qx, qy, m)) continue;
+                if (!consistent(vj, p, X, n, q, qx, qy, m)) continue;
                 ++count;
-                S0 += vj.c[0] + m.w * ((vj.bp[0] * qx + vj.bp[1] * qy) + vj.bp[2]);
-                S1 += vj.c[1] + m.w * ((vj.bp[3] * qx + vj.bp[4] * qy) + vj.bp[5]);
-                S2 += vj.c[2] + m.w * ((vj.bp[6] * qx + vj.bp[7] * qy) + vj.bp[8]);
+                const Vec3 Xj = backproject(vj, m.w, qx, qy);
+                S0 += Xj.x;
+                S1 += Xj.y;
+                S2 += Xj.z;
                 N0 += m.x;
                 N1 += m.y;
                 N2 += m.z;
@@ -129,7 +109,7 @@ __global__ __launch_bounds__(kBlock) void evaluate_kernel(const View *__restrict
                     int q;
                     float qx, qy;
                     float4 m;
-                    if (consistent(views[j], p, X0, X1, X2, s.x, s.y, s.z, q, qx, qy, m)) used[(size_t)j * npix + q] = 1;
+                    if (consistent(views[j], p, X, n, q, qx, qy, m)) used[(size_t)j * npix + q] = 1;
                 }
             }
         }
@@ -202,27 +182,6 @@ struct gipuma_hip_fusion {
 
 namespace {
 
-int fail(int code, const char *fmt, const char *a = "")
-{
-    char buf[512];
-    snprintf(buf, sizeof buf, fmt, a);
-    gipuma_set_last_error(buf);
-    return code;
-}
-
-#define FUSE_OK(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(GIPUMA_HIP_ERR_DEVICE, #expr ": %s", hipGetErrorString(e_)); \
-    } while (0)
-
-int device_count()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
 // the call's scratch: freed on every way out of gipuma_hip_fuse
 struct Scratch {
     fuse::View *views = nullptr;
@@ -255,12 +214,12 @@ int run(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion *f)
     f->cols = d->cols;
     f->n_views = V;
     f->per_view.assign(V, 0);
-    FUSE_OK(hipSetDevice(d->device_id));
+    HIP_OK(hipSetDevice(d->device_id));
     Scratch sc;
     if (d->stream) {
         sc.st = (hipStream_t)d->stream;
     } else {
-        FUSE_OK(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
+        HIP_OK(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
         sc.st = sc.own;
     }
     hipStream_t st = sc.st;
@@ -286,36 +245,36 @@ int run(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion *f)
     p.depth_min = d->depth_min;
     p.depth_max = d->depth_max;
 
-    FUSE_OK(hipMalloc(&sc.views, sizeof(fuse::View) * V));
-    FUSE_OK(hipMalloc(&sc.stage, sizeof(float4) * 2 * (size_t)npix));
-    FUSE_OK(hipMalloc(&sc.flags, (size_t)npix));
-    FUSE_OK(hipMalloc(&sc.counts, sizeof(uint32_t) * nblocks));
-    FUSE_OK(hipMalloc(&sc.offsets, sizeof(uint32_t) * nblocks));
-    FUSE_OK(hipMalloc(&sc.total, sizeof(uint32_t)));
-    FUSE_OK(hipMalloc(&f->used, (size_t)V * npix));
+    HIP_OK(hipMalloc(&sc.views, sizeof(fuse::View) * V));
+    HIP_OK(hipMalloc(&sc.stage, sizeof(float4) * 2 * (size_t)npix));
+    HIP_OK(hipMalloc(&sc.flags, (size_t)npix));
+    HIP_OK(hipMalloc(&sc.counts, sizeof(uint32_t) * nblocks));
+    HIP_OK(hipMalloc(&sc.offsets, sizeof(uint32_t) * nblocks));
+    HIP_OK(hipMalloc(&sc.total, sizeof(uint32_t)));
+    HIP_OK(hipMalloc(&f->used, (size_t)V * npix));
     int64_t capacity = npix;
-    FUSE_OK(hipMalloc(&f->points, sizeof(float4) * 2 * (size_t)capacity));
-    FUSE_OK(hipEventCreate(&sc.e0));
-    FUSE_OK(hipEventCreate(&sc.e1));
-    FUSE_OK(hipMemcpyAsync(sc.views, table.data(), sizeof(fuse::View) * V, hipMemcpyHostToDevice, st));
-    FUSE_OK(hipMemsetAsync(f->used, 0, (size_t)V * npix, st));
+    HIP_OK(hipMalloc(&f->points, sizeof(float4) * 2 * (size_t)capacity));
+    HIP_OK(hipEventCreate(&sc.e0));
+    HIP_OK(hipEventCreate(&sc.e1));
+    HIP_OK(hipMemcpyAsync(sc.views, table.data(), sizeof(fuse::View) * V, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(f->used, 0, (size_t)V * npix, st));
 
-    FUSE_OK(hipEventRecord(sc.e0, st));
+    HIP_OK(hipEventRecord(sc.e0, st));
     for (int i = 0; i < V; ++i) {
         hipLaunchKernelGGL(fuse::evaluate_kernel, dim3(nblocks), dim3(fuse::kBlock), 0, st, sc.views, p, i, f->used, sc.stage,
                            sc.flags, sc.counts);
-        FUSE_OK(hipGetLastError());
+        HIP_OK(hipGetLastError());
         hipLaunchKernelGGL(fuse::scan_kernel, dim3(1), dim3(fuse::kScan), 0, st, sc.counts, sc.offsets, nblocks, sc.total);
-        FUSE_OK(hipGetLastError());
+        HIP_OK(hipGetLastError());
         uint32_t n = 0;
-        FUSE_OK(hipMemcpyAsync(&n, sc.total, sizeof n, hipMemcpyDeviceToHost, st));
-        FUSE_OK(hipStreamSynchronize(st));
-        if (n > (uint32_t)npix) return fail(GIPUMA_HIP_ERR_DEVICE, "fusion: a view emitted more points than it has pixels%s");
+        HIP_OK(hipMemcpyAsync(&n, sc.total, sizeof n, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (n > (uint32_t)npix) return fail(GIPUMA_HIP_ERR_DEVICE, "fusion: a view emitted more points than it has pixels");
         if (f->n_points + n > capacity) {  // grow (doubling), keeping the points of the earlier views
             int64_t want = capacity;
             while (want < f->n_points + n) want *= 2;
             float4 *grown = nullptr;
-            FUSE_OK(hipMalloc(&grown, sizeof(float4) * 2 * (size_t)want));
+            HIP_OK(hipMalloc(&grown, sizeof(float4) * 2 * (size_t)want));
             hipError_t e = hipMemcpyAsync(grown, f->points, sizeof(float4) * 2 * (size_t)f->n_points, hipMemcpyDeviceToDevice, st);
             if (e == hipSuccess) e = hipStreamSynchronize(st);
             if (e != hipSuccess) {
@@ -329,14 +288,14 @@ int run(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion *f)
         if (n) {
             hipLaunchKernelGGL(fuse::scatter_kernel, dim3(nblocks), dim3(fuse::kBlock), 0, st, sc.flags, sc.stage, sc.offsets, npix,
                                f->points + 2 * f->n_points);
-            FUSE_OK(hipGetLastError());
+            HIP_OK(hipGetLastError());
         }
         f->per_view[i] = n;
         f->n_points += n;
     }
-    FUSE_OK(hipEventRecord(sc.e1, st));
-    FUSE_OK(hipStreamSynchronize(st));
-    FUSE_OK(hipEventElapsedTime(&f->ms, sc.e0, sc.e1));
+    HIP_OK(hipEventRecord(sc.e1, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipEventElapsedTime(&f->ms, sc.e0, sc.e1));
     return 0;
 }
 
@@ -346,24 +305,23 @@ extern "C" {
 
 int gipuma_hip_fuse(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion **out)
 {
-    if (!out) return fail(GIPUMA_HIP_ERR_ARG, "null out pointer%s");
+    if (!out) return fail(GIPUMA_HIP_ERR_ARG, "null out pointer");
     *out = nullptr;
-    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor%s");
-    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "fusion: abi_version mismatch%s");
+    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
+    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "fusion: abi_version mismatch");
     if (d->rows < 1 || d->cols < 1 || (int64_t)d->rows * d->cols > (1ll << 30))
-        return fail(GIPUMA_HIP_ERR_ARG, "fusion: rows x cols out of range%s");
+        return fail(GIPUMA_HIP_ERR_ARG, "fusion: rows x cols out of range");
     if (d->n_views < 2 || d->n_views > GIPUMA_HIP_FUSION_MAX_VIEWS)
-        return fail(GIPUMA_HIP_ERR_ARG, "fusion: n_views must be 2..512 (MAX_IMAGES)%s");
-    if (d->num_consistent < 1) return fail(GIPUMA_HIP_ERR_ARG, "fusion: num_consistent must be >= 1%s");
-    if (!d->views) return fail(GIPUMA_HIP_ERR_ARG, "fusion: null views%s");
+        return fail(GIPUMA_HIP_ERR_ARG, "fusion: n_views must be 2..512 (MAX_IMAGES)");
+    if (d->num_consistent < 1) return fail(GIPUMA_HIP_ERR_ARG, "fusion: num_consistent must be >= 1");
+    if (!d->views) return fail(GIPUMA_HIP_ERR_ARG, "fusion: null views");
     for (int v = 0; v < d->n_views; ++v)
-        if (!d->views[v].norm4) return fail(GIPUMA_HIP_ERR_ARG, "fusion: a view without a norm4 plane%s");
+        if (!d->views[v].norm4) return fail(GIPUMA_HIP_ERR_ARG, "fusion: a view without a norm4 plane");
     if (!(d->disp_thresh >= 0.f) || !(d->normal_thresh >= 0.f))
-        return fail(GIPUMA_HIP_ERR_ARG, "fusion: thresholds must be >= 0%s");
-    if (device_count() < 1) return fail(GIPUMA_HIP_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback%s");
-    if (d->device_id < 0 || d->device_id >= device_count()) return fail(GIPUMA_HIP_ERR_ARG, "device_id out of range%s");
+        return fail(GIPUMA_HIP_ERR_ARG, "fusion: thresholds must be >= 0");
+    if (const int rc = pm_host::check_device(d->device_id)) return rc;
     gipuma_hip_fusion *f = new (std::nothrow) gipuma_hip_fusion;
-    if (!f) return fail(GIPUMA_HIP_ERR_DEVICE, "out of host memory%s");
+    if (!f) return fail(GIPUMA_HIP_ERR_DEVICE, "out of host memory");
     const int rc = run(d, f);
     if (rc) {
         gipuma_hip_fusion_free(f);
@@ -375,7 +333,7 @@ int gipuma_hip_fuse(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion **out)
 
 int gipuma_hip_fusion_count(const gipuma_hip_fusion *f, int64_t *n_points, int64_t *per_view, float *device_ms)
 {
-    if (!f) return fail(GIPUMA_HIP_ERR_ARG, "null fusion handle%s");
+    if (!f) return fail(GIPUMA_HIP_ERR_ARG, "null fusion handle");
     if (n_points) *n_points = f->n_points;
     if (per_view) memcpy(per_view, f->per_view.data(), sizeof(int64_t) * f->per_view.size());
     if (device_ms) *device_ms = f->ms;
@@ -384,12 +342,12 @@ int gipuma_hip_fusion_count(const gipuma_hip_fusion *f, int64_t *n_points, int64
 
 int gipuma_hip_fusion_points(const gipuma_hip_fusion *f, void *vertices, int64_t first, int64_t count)
 {
-    if (!f || (!vertices && count)) return fail(GIPUMA_HIP_ERR_ARG, "null argument%s");
-    if (first < 0 || count < 0 || first > f->n_points - count) return fail(GIPUMA_HIP_ERR_ARG, "fusion: point range out of bounds%s");
+    if (!f || (!vertices && count)) return fail(GIPUMA_HIP_ERR_ARG, "null argument");
+    if (first < 0 || count < 0 || first > f->n_points - count) return fail(GIPUMA_HIP_ERR_ARG, "fusion: point range out of bounds");
     if (!count) return 0;
-    FUSE_OK(hipSetDevice(f->device));
+    HIP_OK(hipSetDevice(f->device));
     std::vector<float4> rec(2 * (size_t)count);
-    FUSE_OK(hipMemcpy(rec.data(), f->points + 2 * first, sizeof(float4) * rec.size(), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rec.data(), f->points + 2 * first, sizeof(float4) * rec.size(), hipMemcpyDeviceToHost));
     unsigned char *o = (unsigned char *)vertices;
     for (int64_t k = 0; k < count; ++k, o += 27) {
         const float4 a = rec[2 * k], b = rec[2 * k + 1];
@@ -402,9 +360,9 @@ int gipuma_hip_fusion_points(const gipuma_hip_fusion *f, void *vertices, int64_t
 
 int gipuma_hip_fusion_used(const gipuma_hip_fusion *f, uint8_t *masks)
 {
-    if (!f || !masks) return fail(GIPUMA_HIP_ERR_ARG, "null argument%s");
-    FUSE_OK(hipSetDevice(f->device));
-    FUSE_OK(hipMemcpy(masks, f->used, (size_t)f->n_views * f->rows * f->cols, hipMemcpyDeviceToHost));
+    if (!f || !masks) return fail(GIPUMA_HIP_ERR_ARG, "null argument");
+    HIP_OK(hipSetDevice(f->device));
+    HIP_OK(hipMemcpy(masks, f->used, (size_t)f->n_views * f->rows * f->cols, hipMemcpyDeviceToHost));
     return 0;
 }
 

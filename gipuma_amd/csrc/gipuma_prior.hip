@@ -20,15 +20,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <mutex>
 
-#include "../../include/gipuma_hip.h"
+#include "pm_host.h"
+#include "pm_view.h"
 
-// the library's last-error text (gipuma_hip.hip; hidden, not part of the C-ABI)
-extern "C" __attribute__((visibility("hidden"))) void gipuma_set_last_error(const char *text);
+using pm_host::fail;
 
 namespace prior {
 
@@ -38,17 +37,7 @@ constexpr unsigned long long kEmpty = ~0ull;
 // the slots up: one word takes about 90 atomics per microsecond, and a 1600x1200 frame has 30 000 wavefronts.
 constexpr int kSlots = 256;
 
-// Loads through the global address space: a pointer held as an integer is a generic one to the compiler, and its
-// accesses would be flat_* (gipuma_fuse.hip, pm_core.h DevPtr).
-template <class T>
-__device__ __forceinline__ T load_global(uint64_t base, int idx)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return ((const __attribute__((address_space(1))) T *)base)[idx];
-#else
-    return ((const T *)base)[idx];
-#endif
-}
+using namespace pm_view;  // the contract's operation order: load_global, valid_depth, ray, backproject, project, dot
 
 struct Source {  // 64 bytes
     uint64_t norm4, cost;
@@ -64,11 +53,6 @@ struct Args {  // passed by value: the kernel argument segment (2.2 KB of its 4 
     Source src[GIPUMA_HIP_MAX_VIEWS];
 };
 
-__device__ __forceinline__ bool valid(float z, float depth_min, float depth_max)
-{
-    return isfinite(z) && z > 0.f && (depth_min <= 0.f || z >= depth_min) && (depth_max <= 0.f || z <= depth_max);
-}
-
 __global__ __launch_bounds__(kBlock) void splat_kernel(Args a, unsigned long long *__restrict__ zbuf)
 {
     const int npix = a.rows * a.cols;
@@ -78,29 +62,20 @@ __global__ __launch_bounds__(kBlock) void splat_kernel(Args a, unsigned long lon
     const Source &s = a.src[k];
     const float4 m = load_global<float4>(s.norm4, idx);
     const float z = m.w;
-    if (!valid(z, a.depth_min, a.depth_max)) return;
-    if (!(isfinite(m.x) && isfinite(m.y) && isfinite(m.z))) return;
-    if (!((m.x * m.x + m.y * m.y) + m.z * m.z > 0.f)) return;
+    const Vec3 n = {m.x, m.y, m.z};
+    if (!valid_depth(z, a.depth_min, a.depth_max)) return;
+    if (!(isfinite(n.x) && isfinite(n.y) && isfinite(n.z))) return;
+    if (!(dot(n, n) > 0.f)) return;
     if (s.cost && !(load_global<float>(s.cost, idx) <= a.max_cost)) return;
-    const float xf = (float)(idx % a.cols), yf = (float)(idx / a.cols);
-    const float X0 = s.c[0] + z * ((s.bp[0] * xf + s.bp[1] * yf) + s.bp[2]);
-    const float X1 = s.c[1] + z * ((s.bp[3] * xf + s.bp[4] * yf) + s.bp[5]);
-    const float X2 = s.c[2] + z * ((s.bp[6] * xf + s.bp[7] * yf) + s.bp[8]);
-    const Target &t = a.t;
-    const float h0 = ((t.P[0] * X0 + t.P[1] * X1) + t.P[2] * X2) + t.P[3];
-    const float h1 = ((t.P[4] * X0 + t.P[5] * X1) + t.P[6] * X2) + t.P[7];
-    const float h2 = ((t.P[8] * X0 + t.P[9] * X1) + t.P[10] * X2) + t.P[11];
-    if (!(h2 > 0.f) || !valid(h2, a.depth_min, a.depth_max)) return;
-    const float qx = floorf(h0 / h2 + 0.5f);
-    const float qy = floorf(h1 / h2 + 0.5f);
+    const Vec3 X = backproject(s, z, (float)(idx % a.cols), (float)(idx / a.cols));
+    const Vec3 h = project(a.t, X);
+    if (!(h.z > 0.f) || !valid_depth(h.z, a.depth_min, a.depth_max)) return;
+    const float qx = floorf(h.x / h.z + 0.5f);
+    const float qy = floorf(h.y / h.z + 0.5f);
     if (!(qx >= 0.f && qx < (float)a.cols && qy >= 0.f && qy < (float)a.rows)) return;
-    const float r0 = (t.bp[0] * qx + t.bp[1] * qy) + t.bp[2];
-    const float r1 = (t.bp[3] * qx + t.bp[4] * qy) + t.bp[5];
-    const float r2 = (t.bp[6] * qx + t.bp[7] * qy) + t.bp[8];
-    const float den = (m.x * r0 + m.y * r1) + m.z * r2;
-    if (!(den < 0.f)) return;  // the surface does not face the target camera
+    if (!(dot(n, ray(a.t, qx, qy)) < 0.f)) return;  // the surface does not face the target camera
     const unsigned long long key =
-        ((unsigned long long)__float_as_uint(h2) << 32) | (unsigned long long)((uint32_t)k * (uint32_t)npix + (uint32_t)idx);
+        ((unsigned long long)__float_as_uint(h.z) << 32) | (unsigned long long)((uint32_t)k * (uint32_t)npix + (uint32_t)idx);
     // (qx, qy) passed the bounds test above: the index is inside zbuf's rows * cols entries
     atomicMin(&zbuf[(size_t)((int)qy * a.cols + (int)qx)], key);
 }
@@ -136,22 +111,13 @@ __global__ __launch_bounds__(kBlock) void resolve_kernel(Args a, const unsigned 
             const int k = (int)(low / (uint32_t)npix), idx = (int)(low % (uint32_t)npix);  // k < n_sources: splat wrote it
             const Source &s = a.src[k];
             const float4 m = load_global<float4>(s.norm4, idx);
-            const float z = m.w;
-            const float xs = (float)(idx % a.cols), ys = (float)(idx / a.cols);
-            const float X0 = s.c[0] + z * ((s.bp[0] * xs + s.bp[1] * ys) + s.bp[2]);
-            const float X1 = s.c[1] + z * ((s.bp[3] * xs + s.bp[4] * ys) + s.bp[5]);
-            const float X2 = s.c[2] + z * ((s.bp[6] * xs + s.bp[7] * ys) + s.bp[8]);
+            const Vec3 n = {m.x, m.y, m.z};
+            const Vec3 X = backproject(s, m.w, (float)(idx % a.cols), (float)(idx / a.cols));
             const Target &t = a.t;
-            const float xf = (float)x, yf = (float)y;
-            const float r0 = (t.bp[0] * xf + t.bp[1] * yf) + t.bp[2];
-            const float r1 = (t.bp[3] * xf + t.bp[4] * yf) + t.bp[5];
-            const float r2 = (t.bp[6] * xf + t.bp[7] * yf) + t.bp[8];
-            const float den = (m.x * r0 + m.y * r1) + m.z * r2;
-            const float num = (m.x * (X0 - t.c[0]) + m.y * (X1 - t.c[1])) + m.z * (X2 - t.c[2]);
-            const float zc = num / den;
-            const float nn = (m.x * m.x + m.y * m.y) + m.z * m.z;
-            const float rr = (r0 * r0 + r1 * r1) + r2 * r2;
-            const bool good = den * den > a.g2 * (nn * rr) && valid(zc, a.depth_min, a.depth_max);
+            const Vec3 r = ray(t, (float)x, (float)y);
+            const float den = dot(n, r);
+            const float zc = dot(n, Vec3{X.x - t.c[0], X.y - t.c[1], X.z - t.c[2]}) / den;
+            const bool good = den * den > a.g2 * (dot(n, n) * dot(r, r)) && valid_depth(zc, a.depth_min, a.depth_max);
             if (cls == 0)
                 res = make_float4(m.x, m.y, m.z, good ? zc : __uint_as_float((uint32_t)(key >> 32)));
             else if (good)
@@ -171,27 +137,6 @@ __global__ __launch_bounds__(kBlock) void resolve_kernel(Args a, const unsigned 
 }  // namespace prior
 
 namespace {
-
-int fail(int code, const char *fmt, const char *a = "")
-{
-    char buf[512];
-    snprintf(buf, sizeof buf, fmt, a);
-    gipuma_set_last_error(buf);
-    return code;
-}
-
-#define PRIOR_OK(expr)                                                                                 \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(GIPUMA_HIP_ERR_DEVICE, #expr ": %s", hipGetErrorString(e_)); \
-    } while (0)
-
-int device_count()
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
 
 // The scratch of a device, kept between calls (a call that frees would have to wait for the device): the key plane, grown
 // when a larger frame comes, the counts and the event pair.  Calls on one device share it, so they must not overlap.
@@ -216,17 +161,17 @@ int run(const gipuma_hip_prior_desc *d, float *prior_dev, int64_t counts[3], flo
     }
     Scratch &sc = *found;
     std::lock_guard<std::mutex> lock(sc.mutex);
-    PRIOR_OK(hipSetDevice(d->device_id));
+    HIP_OK(hipSetDevice(d->device_id));
     if (sc.capacity < npix) {
-        if (sc.zbuf) PRIOR_OK(hipFree(sc.zbuf));  // (waits for the calls that still use it)
+        if (sc.zbuf) HIP_OK(hipFree(sc.zbuf));  // (waits for the calls that still use it)
         sc.zbuf = nullptr;
         sc.capacity = 0;
-        PRIOR_OK(hipMalloc(&sc.zbuf, sizeof(unsigned long long) * npix));
+        HIP_OK(hipMalloc(&sc.zbuf, sizeof(unsigned long long) * npix));
         sc.capacity = npix;
     }
-    if (!sc.counts) PRIOR_OK(hipMalloc(&sc.counts, sizeof(uint32_t) * 3 * prior::kSlots));
-    if (!sc.e0) PRIOR_OK(hipEventCreate(&sc.e0));
-    if (!sc.e1) PRIOR_OK(hipEventCreate(&sc.e1));
+    if (!sc.counts) HIP_OK(hipMalloc(&sc.counts, sizeof(uint32_t) * 3 * prior::kSlots));
+    if (!sc.e0) HIP_OK(hipEventCreate(&sc.e0));
+    if (!sc.e1) HIP_OK(hipEventCreate(&sc.e1));
 
     prior::Args a;
     memset(&a, 0, sizeof a);
@@ -249,29 +194,29 @@ int run(const gipuma_hip_prior_desc *d, float *prior_dev, int64_t counts[3], flo
     }
     hipStream_t st = (hipStream_t)d->stream;
     const int nblocks = (int)((npix + prior::kBlock - 1) / prior::kBlock);
-    if (device_ms) PRIOR_OK(hipEventRecord(sc.e0, st));
-    PRIOR_OK(hipMemsetAsync(sc.zbuf, 0xFF, sizeof(unsigned long long) * npix, st));
-    PRIOR_OK(hipMemsetAsync(sc.counts, 0, sizeof(uint32_t) * 3 * prior::kSlots, st));
+    if (device_ms) HIP_OK(hipEventRecord(sc.e0, st));
+    HIP_OK(hipMemsetAsync(sc.zbuf, 0xFF, sizeof(unsigned long long) * npix, st));
+    HIP_OK(hipMemsetAsync(sc.counts, 0, sizeof(uint32_t) * 3 * prior::kSlots, st));
     hipLaunchKernelGGL(prior::splat_kernel, dim3(nblocks, S), dim3(prior::kBlock), 0, st, a, sc.zbuf);
-    PRIOR_OK(hipGetLastError());
+    HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(prior::resolve_kernel, dim3(nblocks), dim3(prior::kBlock), 0, st, a, sc.zbuf, (float4 *)prior_dev,
                        sc.counts);
-    PRIOR_OK(hipGetLastError());
-    if (device_ms) PRIOR_OK(hipEventRecord(sc.e1, st));
+    HIP_OK(hipGetLastError());
+    if (device_ms) HIP_OK(hipEventRecord(sc.e1, st));
     if (counts) {
         uint32_t c[3 * prior::kSlots];
-        PRIOR_OK(hipMemcpyAsync(c, sc.counts, sizeof c, hipMemcpyDeviceToHost, st));
-        PRIOR_OK(hipStreamSynchronize(st));
+        HIP_OK(hipMemcpyAsync(c, sc.counts, sizeof c, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
         for (int i = 0; i < 3; ++i) {
             counts[i] = 0;
             for (int k = 0; k < prior::kSlots; ++k) counts[i] += c[i * prior::kSlots + k];
         }
     }
     if (device_ms) {
-        PRIOR_OK(hipStreamSynchronize(st));
-        PRIOR_OK(hipEventElapsedTime(device_ms, sc.e0, sc.e1));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(device_ms, sc.e0, sc.e1));
     }
-    if (!d->stream) PRIOR_OK(hipStreamSynchronize(st));  // the null stream: complete on return (gipuma_hip_downsample)
+    if (!d->stream) HIP_OK(hipStreamSynchronize(st));  // the null stream: complete on return (gipuma_hip_downsample)
     return 0;
 }
 
@@ -279,23 +224,22 @@ int run(const gipuma_hip_prior_desc *d, float *prior_dev, int64_t counts[3], flo
 
 extern "C" int gipuma_hip_prior_from_views(const gipuma_hip_prior_desc *d, float *prior_dev, int64_t counts[3], float *device_ms)
 {
-    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor%s");
-    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "prior: abi_version mismatch%s");
+    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
+    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "prior: abi_version mismatch");
     if (d->rows < 1 || d->cols < 1 || (int64_t)d->rows * d->cols > (1ll << 30))
-        return fail(GIPUMA_HIP_ERR_ARG, "prior: rows x cols out of range%s");
-    if (d->n_sources < 1 || d->n_sources > GIPUMA_HIP_MAX_VIEWS) return fail(GIPUMA_HIP_ERR_ARG, "prior: n_sources must be 1..32%s");
-    if (!d->sources) return fail(GIPUMA_HIP_ERR_ARG, "prior: null sources%s");
+        return fail(GIPUMA_HIP_ERR_ARG, "prior: rows x cols out of range");
+    if (d->n_sources < 1 || d->n_sources > GIPUMA_HIP_MAX_VIEWS) return fail(GIPUMA_HIP_ERR_ARG, "prior: n_sources must be 1..32");
+    if (!d->sources) return fail(GIPUMA_HIP_ERR_ARG, "prior: null sources");
     for (int k = 0; k < d->n_sources; ++k) {
-        if (!d->sources[k].norm4) return fail(GIPUMA_HIP_ERR_ARG, "prior: a source without a norm4 plane%s");
-        if (d->costs && !d->costs[k]) return fail(GIPUMA_HIP_ERR_ARG, "prior: costs given, but a source without a cost plane%s");
+        if (!d->sources[k].norm4) return fail(GIPUMA_HIP_ERR_ARG, "prior: a source without a norm4 plane");
+        if (d->costs && !d->costs[k]) return fail(GIPUMA_HIP_ERR_ARG, "prior: costs given, but a source without a cost plane");
     }
-    if (d->costs && d->max_cost != d->max_cost) return fail(GIPUMA_HIP_ERR_ARG, "prior: max_cost is not a number%s");
-    if (!(d->grazing_cos >= 0.f && d->grazing_cos <= 1.f)) return fail(GIPUMA_HIP_ERR_ARG, "prior: grazing_cos must be in 0..1%s");
-    if (d->fill != 0 && d->fill != 1) return fail(GIPUMA_HIP_ERR_ARG, "prior: fill must be 0 or 1%s");
-    if (!prior_dev) return fail(GIPUMA_HIP_ERR_ARG, "prior: null output plane%s");
+    if (d->costs && d->max_cost != d->max_cost) return fail(GIPUMA_HIP_ERR_ARG, "prior: max_cost is not a number");
+    if (!(d->grazing_cos >= 0.f && d->grazing_cos <= 1.f)) return fail(GIPUMA_HIP_ERR_ARG, "prior: grazing_cos must be in 0..1");
+    if (d->fill != 0 && d->fill != 1) return fail(GIPUMA_HIP_ERR_ARG, "prior: fill must be 0 or 1");
+    if (!prior_dev) return fail(GIPUMA_HIP_ERR_ARG, "prior: null output plane");
     if ((int64_t)d->n_sources * d->rows * d->cols >= (1ll << 32))
-        return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "prior: n_sources x rows x cols must stay below 2^32 (the key's low word)%s");
-    if (device_count() < 1) return fail(GIPUMA_HIP_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback%s");
-    if (d->device_id < 0 || d->device_id >= device_count()) return fail(GIPUMA_HIP_ERR_ARG, "device_id out of range%s");
+        return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "prior: n_sources x rows x cols must stay below 2^32 (the key's low word)");
+    if (const int rc = pm_host::check_device(d->device_id)) return rc;
     return run(d, prior_dev, counts, device_ms);
 }

@@ -14,13 +14,9 @@
 // kernel reads every input byte once, no LDS, no atomics.
 #include <hip/hip_runtime.h>
 
-#include <cstdint>
-#include <cstdio>
+#include "pm_host.h"
 
-#include "../../include/gipuma_hip.h"
-
-// the library's last-error text (gipuma_hip.hip; hidden, not part of the C-ABI)
-extern "C" __attribute__((visibility("hidden"))) void gipuma_set_last_error(const char *text);
+using pm_host::fail;
 
 namespace pyr {
 
@@ -97,20 +93,6 @@ __global__ __launch_bounds__(kBlockX *kBlockY) void downsample2_kernel(const flo
 
 namespace {
 
-int fail(int code, const char *fmt, const char *a = "")
-{
-    char buf[512];
-    snprintf(buf, sizeof buf, fmt, a);
-    gipuma_set_last_error(buf);
-    return code;
-}
-
-#define PYR_OK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return fail(GIPUMA_HIP_ERR_DEVICE, #expr ": %s", hipGetErrorString(e_)); \
-    } while (0)
-
 bool aligned(const void *p, int pitch, int floats) { return (uintptr_t)p % (4u * floats) == 0 && pitch % floats == 0; }
 
 }  // namespace
@@ -120,17 +102,14 @@ extern "C" {
 int gipuma_hip_downsample(const float *src_dev, int rows, int cols, int pitch, int channels, float *dst_dev, int dst_pitch,
                           int device_id, void *stream)
 {
-    if (!src_dev || !dst_dev) return fail(GIPUMA_HIP_ERR_ARG, "downsample: null plane%s");
-    if (channels != 1 && channels != 4) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "downsample: channels must be 1 or 4%s");
-    if (rows < 2 || cols < 2 || rows > 32768 || cols > 32768) return fail(GIPUMA_HIP_ERR_ARG, "downsample: rows x cols out of range%s");
+    if (!src_dev || !dst_dev) return fail(GIPUMA_HIP_ERR_ARG, "downsample: null plane");
+    if (channels != 1 && channels != 4) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "downsample: channels must be 1 or 4");
+    if (rows < 2 || cols < 2 || rows > 32768 || cols > 32768) return fail(GIPUMA_HIP_ERR_ARG, "downsample: rows x cols out of range");
     const int orows = rows >> 1, ocols = cols >> 1;
     if (pitch < cols * channels || dst_pitch < ocols * channels)
-        return fail(GIPUMA_HIP_ERR_ARG, "downsample: a pitch (in floats) is shorter than its row%s");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-        return fail(GIPUMA_HIP_ERR_NO_DEVICE, "no HIP device visible; this library has no CPU fallback%s");
-    if (device_id < 0 || device_id >= n) return fail(GIPUMA_HIP_ERR_ARG, "device_id out of range%s");
-    PYR_OK(hipSetDevice(device_id));
+        return fail(GIPUMA_HIP_ERR_ARG, "downsample: a pitch (in floats) is shorter than its row");
+    if (const int rc = pm_host::check_device(device_id)) return rc;
+    HIP_OK(hipSetDevice(device_id));
     hipStream_t st = (hipStream_t)stream;
     const bool in16 = aligned(src_dev, pitch, 4), in8 = aligned(src_dev, pitch, 2);
     const bool two = channels == 1 && in16 && aligned(dst_dev, dst_pitch, 2);  // two output pixels per lane
@@ -144,8 +123,8 @@ int gipuma_hip_downsample(const float *src_dev, int rows, int cols, int pitch, i
     else
         k = in8 ? pyr::downsample2_kernel<1, 2> : pyr::downsample2_kernel<1, 1>;
     hipLaunchKernelGGL(k, grid, block, 0, st, src_dev, orows, ocols, pitch, dst_dev, dst_pitch);
-    PYR_OK(hipGetLastError());
-    if (!st) PYR_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    if (!st) HIP_OK(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -16,7 +16,6 @@ Output: the binary PLY (xyz, normal, gray x 3) and a JSON report next to it (<ou
 import argparse
 import ctypes as C
 import json
-import math
 import os
 import re
 import sys
@@ -25,26 +24,12 @@ import time
 import numpy as np
 
 from . import abi, dmb
-from .cameras import decompose_projection, read_p_file, scale_k
-
-BASELINE = 0.54  # cameraGeometryUtils.h:305
-
-
-def view_constants(P, cam_scale=1.0):
-    """The float32 constants of one view, the only place they are made: from P = K [R | -R C] (not re-centred), K scaled
-    by cam_scale, in float64, rounded once.  bp = R^T K^-1, c = C, P = [K R | -K R C], fb = f32(f32(K[0][0]) * 0.54f)."""
-    K, R, Cc = decompose_projection(P)
-    K = scale_k(K, cam_scale)
-    KR = K @ R
-    f32 = np.float32
-    return dict(bp=(R.T @ np.linalg.inv(K)).astype(f32), c=Cc.astype(f32),
-                P=np.concatenate([KR, (-KR @ Cc)[:, None]], axis=1).astype(f32),
-                fb=f32(f32(K[0, 0]) * f32(BASELINE)))
+from .cameras import BASELINE, cos_f32, read_p_file, view_constants  # noqa: F401 (names kept importable from here)
 
 
 def cos_threshold(normal_thresh):
     """cos_t = f32(cos(normal_thresh * pi / 180)) in double, normal_thresh a float32 (what gipuma_hip_fuse computes)"""
-    return np.float32(math.cos(float(np.float32(normal_thresh)) * math.pi / 180.0))
+    return cos_f32(np.float32(normal_thresh))
 
 
 def fuse(norm4s, grays, Ps, cam_scale=1.0, disp_thresh=0.1, normal_thresh=30.0, num_consistent=3, depth_min=-1.0,
@@ -70,24 +55,11 @@ def fuse(norm4s, grays, Ps, cam_scale=1.0, disp_thresh=0.1, normal_thresh=30.0, 
             raise ValueError("every view must have the same size: %s" % (shape[:2],))
     if lib.gipuma_hip_device_count() < 1:
         raise abi.GipumaHipError("depth-map fusion needs a HIP device; gipuma_amd has no CPU fallback")
-    dev = torch.device("cuda", device_id)
-    keep = []  # the device planes handed over, alive until the call returns
-
-    def on_device(a):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-        t = t.to(device=dev, dtype=torch.float32).contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
+    dev, keep = torch.device("cuda", device_id), []  # keep: the device planes handed over, alive until the call returns
     views = (abi.FusionView * V)()
     for v in range(V):
-        k = view_constants(Ps[v], cam_scale)
-        views[v].norm4 = on_device(norm4s[v])
-        views[v].gray = on_device(grays[v]) if grays[v] is not None else None
-        views[v].bp[:] = [float(x) for x in k["bp"].reshape(-1)]
-        views[v].c[:] = [float(x) for x in k["c"]]
-        views[v].P[:] = [float(x) for x in k["P"].reshape(-1)]
-        views[v].fb = float(k["fb"])
+        abi.fill_view(views[v], view_constants(Ps[v], cam_scale), abi.device_plane(norm4s[v], dev, keep),
+                      abi.device_plane(grays[v], dev, keep) if grays[v] is not None else None)
     # (the library works on a stream of its own: the planes must be complete)
     torch.cuda.synchronize(dev)
     d = abi.FusionDesc()

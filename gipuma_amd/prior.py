@@ -10,26 +10,14 @@ in include/gipuma_hip.h).  Pixels no source reaches come out as (0, 0, 0, 0), wh
 of a plain solve.  There is no CPU fallback.
 """
 import ctypes as C
-import math
-
-import numpy as np
 
 from . import abi
-from .fusion import view_constants
+from .cameras import cos_f32, view_constants
 
 
 def grazing_cos(degrees=80.0):
     """f32(cos(degrees)), computed in double"""
-    return float(np.float32(math.cos(float(degrees) * math.pi / 180.0)))
-
-
-def _fill_view(v, k, norm4_ptr=None):
-    v.norm4 = norm4_ptr
-    v.gray = None
-    v.bp[:] = [float(x) for x in k["bp"].reshape(-1)]
-    v.c[:] = [float(x) for x in k["c"]]
-    v.P[:] = [float(x) for x in k["P"].reshape(-1)]
-    v.fb = float(k["fb"])
+    return float(cos_f32(degrees))
 
 
 def prior_from_views(target_P, source_norm4s, source_Ps, cam_scale=1.0, depth_min=-1.0, depth_max=-1.0, costs=None,
@@ -61,21 +49,13 @@ def prior_from_views(target_P, source_norm4s, source_Ps, cam_scale=1.0, depth_mi
             raise ValueError("every view must have the same size: %s" % (shape[:2],))
     if lib.gipuma_hip_device_count() < 1:
         raise abi.GipumaHipError("the cross-view prior needs a HIP device; gipuma_amd has no CPU fallback")
-    dev = torch.device("cuda", device_id)
-    keep = []  # the device planes handed over, alive until the call returns
-
-    def on_device(a):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-        t = t.to(device=dev, dtype=torch.float32).contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
+    dev, keep = torch.device("cuda", device_id), []  # keep: the device planes handed over
     views = (abi.FusionView * S)()
     for k in range(S):
-        _fill_view(views[k], view_constants(source_Ps[k], cam_scale), on_device(source_norm4s[k]))
+        abi.fill_view(views[k], view_constants(source_Ps[k], cam_scale), abi.device_plane(source_norm4s[k], dev, keep))
     cost_ptrs = None
     if costs is not None:
-        cost_ptrs = (C.c_void_p * S)(*[on_device(c) for c in costs])
+        cost_ptrs = (C.c_void_p * S)(*[abi.device_plane(c, dev, keep) for c in costs])
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
@@ -83,7 +63,7 @@ def prior_from_views(target_P, source_norm4s, source_Ps, cam_scale=1.0, depth_mi
     d = abi.PriorDesc()
     d.abi_version = abi.ABI_VERSION
     d.rows, d.cols, d.n_sources = shape[0], shape[1], S
-    _fill_view(d.target, view_constants(target_P, cam_scale))
+    abi.fill_view(d.target, view_constants(target_P, cam_scale))
     d.sources = C.cast(views, C.POINTER(abi.FusionView))
     d.costs = C.cast(cost_ptrs, C.POINTER(C.c_void_p)) if cost_ptrs is not None else None
     d.max_cost = float(max_cost) if max_cost is not None else 0.0

@@ -111,6 +111,16 @@ class GlobalState:
         d.flags = flags
         self.desc = d
 
+    @classmethod
+    def on_resident_planes(cls, planes, used, camera_set, params, seed=1, flags=abi.FLAG_CACHE_IMAGES):
+        """Reference view used[0] with the sources used[1:] on `planes`, a scan's images as device tensors that stay put
+        in HBM (bound by address); camera_set: the cameras of `used`.  With FLAG_CACHE_IMAGES what the library derives from
+        a plane (8-bit check, window-packed copy) is made once per image, not once per reference view that uses it."""
+        imgs = [planes[i] for i in used]
+        return cls(imgs, camera_set, list(range(1, len(used))), params, seed=seed, device_ptrs=[t.data_ptr() for t in imgs],
+                   rows=int(imgs[0].shape[0]), cols=int(imgs[0].shape[1]), device_id=imgs[0].device.index, flags=flags,
+                   channels=1 if imgs[0].dim() == 2 else 4)
+
     @property
     def n_pixels(self):
         return self.rows * self.cols

@@ -103,11 +103,7 @@ def level_problem(pyramid, level, P_list, used, ap, iterations, seed, cam_scale=
     cs = level_cameras([P_list[i] for i in used], level, cam_scale)
     ap_l = AlgorithmParameters(**{k: getattr(ap, k) for k in vars(ap)})
     ap_l.iterations = int(iterations)
-    imgs = [pyramid.planes[level][i] for i in used]
-    rows, cols = pyramid.size(level)
-    channels = 1 if imgs[0].dim() == 2 else 4
-    return GlobalState(imgs, cs, list(range(1, len(used))), ap_l, seed=seed, device_ptrs=[t.data_ptr() for t in imgs],
-                       rows=rows, cols=cols, device_id=pyramid.device.index, flags=flags, channels=channels)
+    return GlobalState.on_resident_planes(pyramid.planes[level], used, cs, ap_l, seed=seed, flags=flags)
 
 
 def solve_view(pyramid, P_list, used, ap, level_iterations, seed=1, mode="exact", cam_scale=1.0, timing=True,

@@ -286,7 +286,7 @@ int gipuma_hip_downsample(const float *src_dev, int rows, int cols, int pitch, i
 #define GIPUMA_HIP_FUSION_MAX_VIEWS 512 /* MAX_IMAGES, config.h:2 */
 
 /* One view: device planes and float32 constants derived on the host in double from the view's own (not re-centred)
- * P = K [R | -R C], K scaled by cam_scale (gipuma_amd/fusion.py view_constants). */
+ * P = K [R | -R C], K scaled by cam_scale (gipuma_amd/cameras.py view_constants). */
 typedef struct gipuma_hip_fusion_view {
     const float *norm4; /* device, rows*cols*4 floats (n_world.xyz, depth) as gipuma_hip_finalize leaves them */
     const float *gray;  /* device, rows*cols floats 0..255, or NULL (gray 0) */
@@ -343,7 +343,7 @@ int gipuma_hip_fusion_free(gipuma_hip_fusion *f);
  *            `empty` pixel is (0, 0, 0, 0), which gipuma_hip_seed_planes answers with the random plane of
  *            gipuma_hip_init_planes.
  * target: bp, c and P are read (norm4, gray, fb are not); sources: norm4, bp and c.  The constants are those of
- * gipuma_amd/fusion.py view_constants.  costs: NULL, or a host array of n_sources device planes of rows * cols floats.
+ * gipuma_amd/cameras.py view_constants.  costs: NULL, or a host array of n_sources device planes of rows * cols floats.
  * A frame may have at most 2^30 pixels (pixel indices are int; more is GIPUMA_HIP_ERR_ARG, as in the fusion); within
  * that, n_sources * rows * cols >= 2^32 is refused with GIPUMA_HIP_ERR_UNSUPPORTED (the key's low word). */
 typedef struct gipuma_hip_prior_desc {

@@ -6,35 +6,18 @@ import collections
 import numpy as np
 
 from gipuma_amd import dmb
+from tests.view_ref import backproject, dot, project, valid  # noqa: F401 (backproject: used by tests/test_fusion.py)
 
 f32 = np.float32
 # why a (pixel, partner) pair or a pixel is turned down, in the order the contract tests
 REASONS = ("invalid", "used", "behind", "outside", "partner_invalid", "disparity", "normal", "too_few")
 
 
-class Result:
-    def __init__(self, points, per_view, used, tally):
-        self.points, self.per_view, self.used, self.tally = points, per_view, used, tally
-
-
-def _valid(z, depth_min, depth_max):
-    with np.errstate(invalid="ignore"):
-        ok = np.isfinite(z) & (z > 0)
-        if depth_min > 0:
-            ok &= z >= depth_min
-        if depth_max > 0:
-            ok &= z <= depth_max
-    return ok
-
-
-def backproject(consts, z, xf, yf):
-    """X_k = c_k + z * ((bp[k][0] x + bp[k][1] y) + bp[k][2]), float32"""
-    bp, c = consts["bp"], consts["c"]
-    return [c[k] + z * ((bp[k, 0] * xf + bp[k, 1] * yf) + bp[k, 2]) for k in range(3)]
+Result = collections.namedtuple("Result", "points per_view used tally")
 
 
 def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1.0, depth_max=-1.0):
-    """norm4s: V (rows, cols, 4) float32; grays: (rows, cols) or None; consts: gipuma_amd.fusion.view_constants per view;
+    """norm4s: V (rows, cols, 4) float32; grays: (rows, cols) or None; consts: gipuma_amd.cameras.view_constants per view;
     cos_t: float32 (gipuma_amd.fusion.cos_threshold).  Returns Result(points (PLY vertices, (view, y, x) order),
     per_view counts, used (V, rows, cols) uint8, tally {reason: count})."""
     V = len(norm4s)
@@ -50,7 +33,7 @@ def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1
     out, per_view = [], []
     for i in range(V):
         z_all = planes[i][:, 3]
-        val = _valid(z_all, depth_min, depth_max)
+        val = valid(z_all, depth_min, depth_max)
         tally["invalid"] += int((~val).sum())
         tally["used"] += int((val & (used[i] != 0)).sum())
         idx = np.nonzero(val & (used[i] == 0))[0]
@@ -65,8 +48,8 @@ def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1
         for j in range(V):
             if j == i:
                 continue
-            P, fb = consts[j]["P"], consts[j]["fb"]
-            h = [((P[k, 0] * X[0] + P[k, 1] * X[1]) + P[k, 2] * X[2]) + P[k, 3] for k in range(3)]
+            fb = consts[j]["fb"]
+            h = project(consts[j], X)
             with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
                 front = h[2] > 0
                 qx = np.floor(h[0] / h[2] + f32(0.5))
@@ -77,11 +60,11 @@ def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1
             qxs, qys = np.where(inside, qx, f32(0)), np.where(inside, qy, f32(0))
             q = qys.astype(np.int64) * cols + qxs.astype(np.int64)
             m = planes[j][q]
-            pv = inside & _valid(m[:, 3], depth_min, depth_max)
+            pv = inside & valid(m[:, 3], depth_min, depth_max)
             tally["partner_invalid"] += int((inside & ~pv).sum())
             with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
                 dok = np.abs(fb / h[2] - fb / m[:, 3]) < disp_thresh
-                nok = ((n[0] * m[:, 0] + n[1] * m[:, 1]) + n[2] * m[:, 2]) > cos_t
+                nok = dot(n, [m[:, k] for k in range(3)]) > cos_t
             tally["disparity"] += int((pv & ~dok).sum())
             tally["normal"] += int((pv & dok & ~nok).sum())
             ok = pv & dok & nok
@@ -99,7 +82,7 @@ def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1
         e = np.nonzero(emit)[0]
         k1 = (count[e] + 1).astype(f32)
         with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-            length = np.sqrt((N[0][e] * N[0][e] + N[1][e] * N[1][e]) + N[2][e] * N[2][e])
+            length = np.sqrt(dot([N[k][e] for k in range(3)], [N[k][e] for k in range(3)]))
             v = np.zeros(len(e), dtype=dmb._PLY_VERTEX)
             for k, name in enumerate(("x", "y", "z")):
                 v[name] = S[k][e] / k1

@@ -6,39 +6,15 @@ import collections
 
 import numpy as np
 
+from tests.view_ref import backproject, dot, project, rays, valid
+
 f32 = np.float32
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 # why a source pixel is left out of the splat, in the order the contract tests
 REASONS = ("invalid_depth", "bad_normal", "cost", "behind", "outside", "back_facing")
 
 
-class Result:
-    def __init__(self, prior, counts, zbuf, tally, info):
-        self.prior, self.counts, self.zbuf, self.tally, self.info = prior, counts, zbuf, tally, info
-
-
-def _valid(z, depth_min, depth_max):
-    with np.errstate(invalid="ignore"):
-        ok = np.isfinite(z) & (z > 0)
-        if depth_min > 0:
-            ok &= z >= depth_min
-        if depth_max > 0:
-            ok &= z <= depth_max
-    return ok
-
-
-def _backproject(k, z, xf, yf):
-    bp, c = k["bp"], k["c"]
-    return [c[i] + z * ((bp[i, 0] * xf + bp[i, 1] * yf) + bp[i, 2]) for i in range(3)]
-
-
-def _rays(k, xf, yf):
-    bp = k["bp"]
-    return [(bp[i, 0] * xf + bp[i, 1] * yf) + bp[i, 2] for i in range(3)]
-
-
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+Result = collections.namedtuple("Result", "prior counts zbuf tally info")
 
 
 def grazing_cos(degrees=80.0):
@@ -49,7 +25,7 @@ def grazing_cos(degrees=80.0):
 
 def prior_from_views(target, source_norm4s, sources, depth_min=-1.0, depth_max=-1.0, costs=None, max_cost=None,
                      grazing=None, fill=True):
-    """target / sources: gipuma_amd.fusion.view_constants of the cameras; source_norm4s: (rows, cols, 4) float32 result
+    """target / sources: gipuma_amd.cameras.view_constants of the cameras; source_norm4s: (rows, cols, 4) float32 result
     planes; costs: None or one (rows, cols) plane per source.  Returns Result(prior (rows, cols, 4), counts
     [direct, filled, empty], zbuf, tally {reason: source pixels}, info dict(cls (rows, cols) 0 / 1 / 2, source (rows,
     cols) winner's ordinal or -1, grazing (rows, cols) bool: the plane intersection was turned down))."""
@@ -65,23 +41,22 @@ def prior_from_views(target, source_norm4s, sources, depth_min=-1.0, depth_max=-
     xs, ys = xx.reshape(-1).astype(f32), yy.reshape(-1).astype(f32)
     zbuf = np.full(npix, EMPTY, dtype=np.uint64)
     tally = collections.Counter({r: 0 for r in REASONS})
-    P = target["P"]
     with np.errstate(all="ignore"):
         for k in range(S):
             m = planes[k]
             n, z = [m[:, i] for i in range(3)], m[:, 3]
-            ok = _valid(z, depth_min, depth_max)
+            ok = valid(z, depth_min, depth_max)
             tally["invalid_depth"] += int((~ok).sum())
-            nok = np.isfinite(n[0]) & np.isfinite(n[1]) & np.isfinite(n[2]) & (_dot(n, n) > 0)
+            nok = np.isfinite(n[0]) & np.isfinite(n[1]) & np.isfinite(n[2]) & (dot(n, n) > 0)
             tally["bad_normal"] += int((ok & ~nok).sum())
             ok &= nok
             if costs is not None:
                 cok = np.ascontiguousarray(costs[k], dtype=f32).reshape(-1) <= f32(max_cost)
                 tally["cost"] += int((ok & ~cok).sum())
                 ok &= cok
-            X = _backproject(sources[k], z, xs, ys)
-            h = [((P[i, 0] * X[0] + P[i, 1] * X[1]) + P[i, 2] * X[2]) + P[i, 3] for i in range(3)]
-            front = (h[2] > 0) & _valid(h[2], depth_min, depth_max)
+            X = backproject(sources[k], z, xs, ys)
+            h = project(target, X)
+            front = (h[2] > 0) & valid(h[2], depth_min, depth_max)
             tally["behind"] += int((ok & ~front).sum())
             ok &= front
             qx = np.floor(h[0] / h[2] + f32(0.5))
@@ -89,8 +64,8 @@ def prior_from_views(target, source_norm4s, sources, depth_min=-1.0, depth_max=-
             inside = (qx >= 0) & (qx < f32(cols)) & (qy >= 0) & (qy < f32(rows))
             tally["outside"] += int((ok & ~inside).sum())
             ok &= inside
-            r = _rays(target, qx, qy)
-            facing = _dot(n, r) < 0
+            r = rays(target, qx, qy)
+            facing = dot(n, r) < 0
             tally["back_facing"] += int((ok & ~facing).sum())
             ok &= facing
             idx = np.nonzero(ok)[0]
@@ -124,15 +99,15 @@ def prior_from_views(target, source_norm4s, sources, depth_min=-1.0, depth_max=-
         m = np.stack(planes)[ks, idx]
         n, z = [m[:, i] for i in range(3)], m[:, 3]
         sxs, sys_ = (idx % cols).astype(f32), (idx // cols).astype(f32)
-        bp = np.stack([s["bp"] for s in sources])[ks]
-        c = np.stack([s["c"] for s in sources])[ks]
-        X = [c[:, i] + z * ((bp[:, i, 0] * sxs + bp[:, i, 1] * sys_) + bp[:, i, 2]) for i in range(3)]
-        r = _rays(target, xs, ys)
-        den = _dot(n, r)
+        # (every pixel with the constants of its own winner: bp as (3, 3, npix), c as (3, npix))
+        winner = dict(bp=np.stack([s["bp"] for s in sources])[ks].transpose(1, 2, 0), c=np.stack([s["c"] for s in sources])[ks].T)
+        X = backproject(winner, z, sxs, sys_)
+        r = rays(target, xs, ys)
+        den = dot(n, r)
         ct = target["c"]
-        num = (n[0] * (X[0] - ct[0]) + n[1] * (X[1] - ct[1])) + n[2] * (X[2] - ct[2])
+        num = dot(n, [X[i] - ct[i] for i in range(3)])
         zc = num / den
-        good = (den * den > g2 * (_dot(n, n) * _dot(r, r))) & _valid(zc, depth_min, depth_max)
+        good = (den * den > g2 * (dot(n, n) * dot(r, r))) & valid(zc, depth_min, depth_max)
     cls = cls.reshape(-1)
     direct, filled = have & (cls == 0), have & (cls == 1)
     prior = np.zeros((npix, 4), dtype=f32)

@@ -108,6 +108,20 @@ def test_no_gpu_means_a_loud_error_not_a_fallback():
         lib.gipuma_hip_destroy(h)
 
 
+def test_translation_units_are_listed_once_in_the_build_table():
+    """every gipuma_*.hip under csrc/ is in __graft_entry__.TRANSLATION_UNITS and links into the product, the gather variant
+    differs from the product in the literal flavour's flags only, and scripts/build_variant.sh has no list of its own"""
+    import __graft_entry__ as g
+    on_disk = {f for f in os.listdir(g.CSRC) if f.startswith("gipuma_") and f.endswith(".hip")}
+    product = [(tu, flags) for tu, flags, into in g.TRANSLATION_UNITS if "product" in into]
+    gather = [(tu, flags) for tu, flags, into in g.TRANSLATION_UNITS if "gather" in into]
+    assert {tu for tu, _ in product} == on_disk == {tu for tu, _ in gather}
+    assert len(product) == len(on_disk) == len(gather) and all(flags == [] for _, flags in product)
+    assert [u for u in gather if u not in product] == [("gipuma_hip_literal.hip", ["-DPM_LITERAL_FORCE_GATHER"])]
+    script = open(os.path.join(ROOT, "scripts", "build_variant.sh")).read()
+    assert ".hip" not in script and "build_variant" in script
+
+
 def test_missing_library_raises():
     with pytest.raises(abi.GipumaHipError):
         abi.load_library(os.path.join(ROOT, "gipuma_amd", "csrc", "does_not_exist.so"))

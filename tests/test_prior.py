@@ -493,7 +493,9 @@ def _write_scan(folder, scan):
 def test_batch_view_prior(hip, tmp_path):
     """a 5-view scan, every view a reference: the dumps of every view equal the composition (restated prior from the earlier
     dumps' planes + restated seed + oracle) bit for bit, the order is the greedy one, the report carries the prior's counts;
-    --view_prior 0 writes what batch writes without the option, byte for byte; --view_prior 4 --fuse produces a cloud"""
+    --view_prior 0 writes what batch writes without the option, byte for byte; --view_prior 4 --fuse produces a cloud; with
+    the references given in another order than the scan's, --view_prior --fuse still reports the greedy solve order under
+    "order" (the fusion takes its views in the scan's order, which is not the order they were solved in)"""
     scan = _scan(160, 120, 4)
     tmp = str(tmp_path)
     args = _write_scan(tmp, scan)
@@ -549,3 +551,13 @@ def test_batch_view_prior(hip, tmp_path):
         assert_same(dmb.read_dmb(os.path.join(folder, "cost.dmb")), r_c, "%s cost.dmb" % n)
         done[n] = (np.ascontiguousarray(r_n4), np.ascontiguousarray(r_c))
     assert seeded >= 3 and order[0] == names[0]
+    # the references last to first: the greedy order starts at the scan's last view, the fusion still at its first
+    out_rev = os.path.join(tmp, "prior_rev")
+    assert batch.main(args + ["--output-folder", out_rev, "--views", ",".join(reversed(names)), "--view_prior", "4",
+                              "--prior_iterations", "2", "--fuse", "--disp_thresh=%r" % (0.5 / scan.cam_scale),
+                              "--num_consistent=2"]) == 0
+    rep_rev = json.load(open(os.path.join(out_rev, "batch_rank0.json")))
+    order_rev = prior.greedy_order(names[::-1], {n: [names[i] for i in plans[n][1][1:]] for n in names})
+    assert order_rev[0] == names[-1] and order_rev != names
+    assert rep_rev["order"] == order_rev == [v["ref"] for v in rep_rev["views"]]
+    assert [v["name"] for v in rep_rev["fusion"]["views"]] == names and rep_rev["fusion"]["points"] > 0
