@@ -470,7 +470,7 @@ __device__ __forceinline__ void dbg_add(unsigned long long *p, unsigned long lon
 // or byte offset into a global buffer that the kernels COMPUTE -- the window loads of the packed views, the state planes,
 // the pushed costs, the change flags and rings -- is compared with the extent of its buffer before the access.  A
 // violation is counted per class of access in Problem::viol (the host reports the counts when the session is destroyed:
-// checked_collect in gipuma_hip.hip) and the access goes to element 0 instead.  Without the macro PM_AT(...) is its index and nothing else changes.
+// checked_collect in pm_host_instrument.h) and the access goes to element 0 instead.  Without the macro PM_AT(...) is its index and nothing else changes.
 enum CheckSite { kChkWindow = 0, kChkWindowInt = 1, kChkWindowC4 = 2, kChkNorm4 = 3, kChkCost = 4, kChkPushCost = 5, kChkFlags = 6 };
 #ifdef PM_CHECKED
 template <typename I>

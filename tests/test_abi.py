@@ -145,8 +145,8 @@ def test_product_never_touches_the_oracle():
 
 def test_flag_constants_match_the_header_and_the_other_flavours_are_not_exported():
     """the bindings' GIPUMA_HIP_FLAG_* values are the header's; the library's dynamic symbol table holds the declared C-ABI
-    only -- the entry points of the tolerance-judged and reference-order flavours (gipuma_hipf_*, gipuma_hipl_*, reached
-    through GIPUMA_HIP_FLAG_FAST / _LITERAL) have hidden visibility"""
+    only -- the tolerance-judged and reference-order flavours (reached through GIPUMA_HIP_FLAG_FAST / _LITERAL) show one
+    function each, gipuma_hipf_api / gipuma_hipl_api, the table of their session entry points, with hidden visibility"""
     src = open(HEADER).read()
     flags = {k: int(v) for k, v in re.findall(r"#define\s+GIPUMA_HIP_FLAG_([A-Z_]+)\s+(\d+)u", src)}
     assert flags == {"IMAGES_ON_DEVICE": abi.FLAG_IMAGES_ON_DEVICE, "UNFUSED": abi.FLAG_UNFUSED,
