@@ -538,20 +538,26 @@ def test_push_propagation_edge_cases(hip, cols, rows, sel, over):
     assert_same(c, o_c, "push %dx%d cost" % (cols, rows))
 
 
-@pytest.mark.parametrize("seq", [
+_HISTORY_SEQUENCES = [
     # (iteration, colour, stages) or "set" = write the state back through set_state
     [(0, 0, 7), (0, 1, 7), (1, 0, 7), (1, 0, 7), (1, 1, 7), (1, 1, 7), (2, 0, 7), (2, 1, 7), (3, 0, 7), (3, 1, 7)],
     [(0, 0, 7), (0, 1, 7), (1, 0, 7), (1, 1, 7), (2, 1, 1), (2, 0, 7), (2, 1, 7), (3, 0, 7), (3, 1, 7), (4, 0, 7)],
     [(0, 0, 7), (0, 1, 7), (1, 0, 7), (1, 1, 7), (2, 0, 7), "set", (2, 1, 7), (3, 0, 7), (3, 1, 7), (4, 0, 7)],
     [(0, 1, 7), (0, 1, 7), (0, 0, 7), (1, 1, 7), (1, 0, 7), (2, 1, 7), (2, 0, 7), (3, 1, 7)],
-])
+]
+
+
+@pytest.mark.parametrize("seq", _HISTORY_SEQUENCES)
 @pytest.mark.parametrize("push", [4, 100])
-def test_history_rule_survives_any_launch_sequence(hip, seq, push):
+def test_history_rule_survives_any_launch_sequence(hip, seq, push, grouped=False):
     """rule (H) -- skip a neighbour whose plane did not change in its last half-sweep -- is only
     valid inside a strictly alternating sequence of full half-sweeps; the session must notice
     repeated colours, partial stages and rewritten states by itself.  Each sequence is replayed on
     the oracle launch by launch.  push: the leading half-sweeps that read pushed costs (pm_push.h) --
-    the session must also notice by itself when nobody has offered the costs a half-sweep wants."""
+    the session must also notice by itself when nobody has offered the costs a half-sweep wants.
+    grouped: every half-sweep that is not pushed takes its propagation costs from the plane-keyed kernel (pm_group.h; this
+    frame has fewer than 1024 tiles, so only GIPUMA_HIP_GROUP_FROM reaches it), which applies rule (H) itself, launch by
+    launch -- after a repeated colour, a partial stage or "set" it must do without."""
     gs, _ = synth.build_problem(synth.tiny_config(cols=128, rows=96, n_src=4, blocksize=15, iterations=5,
                                                   n_best=3))
     o = OracleState(gs)
@@ -559,6 +565,8 @@ def test_history_rule_survives_any_launch_sequence(hip, seq, push):
 
     def run():
         with Session(gs) as s:
+            if grouped:  # (the session may drop the plane-keyed kernel by itself: then this test would check nothing new)
+                assert s.schedule()["group_from"] == 0 and s.schedule()["push_launches"] == push
             s.init_planes()
             for step in seq:
                 if step == "set":
@@ -569,9 +577,20 @@ def test_history_rule_survives_any_launch_sequence(hip, seq, push):
                 s.sweep(it, colour, stages)
                 o.sweep(it, colour, stages)
             return s.get_state()
-    n4, c = _with_env({"GIPUMA_HIP_PUSH_LAUNCHES": push}, run)
+    env = {"GIPUMA_HIP_PUSH_LAUNCHES": push}
+    if grouped:
+        env.update({"GIPUMA_HIP_GROUP_FROM": 0, "GIPUMA_HIP_ET_FORCE": 1})
+    n4, c = _with_env(env, run)
     assert_same(n4, o.norm4, "sequence norm4")
     assert_same(c, o.cost, "sequence cost")
+
+
+@pytest.mark.parametrize("seq", _HISTORY_SEQUENCES)
+@pytest.mark.parametrize("push", [0, 4])
+def test_history_rule_survives_any_launch_sequence_grouped(hip, seq, push):
+    """the same sequences with GIPUMA_HIP_GROUP_FROM=0 / GIPUMA_HIP_ET_FORCE=1: rule (H) together with the plane-keyed
+    kernels, launch by launch (push 0: from the first half-sweep on; 4: after the pushed ones)"""
+    test_history_rule_survives_any_launch_sequence(hip, seq, push, grouped=True)
 
 
 @pytest.mark.parametrize("cfg,colour", [
