@@ -13,13 +13,14 @@ f32 = np.float32
 REASONS = ("invalid", "used", "behind", "outside", "partner_invalid", "disparity", "normal", "too_few")
 
 
-Result = collections.namedtuple("Result", "points per_view used tally")
+Result = collections.namedtuple("Result", "points per_view used tally emitted")
 
 
 def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1.0, depth_max=-1.0):
     """norm4s: V (rows, cols, 4) float32; grays: (rows, cols) or None; consts: gipuma_amd.cameras.view_constants per view;
     cos_t: float32 (gipuma_amd.fusion.cos_threshold).  Returns Result(points (PLY vertices, (view, y, x) order),
-    per_view counts, used (V, rows, cols) uint8, tally {reason: count})."""
+    per_view counts, used (V, rows, cols) uint8, tally {reason: count}, emitted (V, rows, cols) uint8: the pixels each view
+    emitted)."""
     V = len(norm4s)
     rows, cols = norm4s[0].shape[:2]
     disp_thresh, cos_t = f32(disp_thresh), f32(cos_t)
@@ -27,6 +28,7 @@ def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1
     planes = [np.ascontiguousarray(n, dtype=f32).reshape(-1, 4) for n in norm4s]
     gplanes = [None if g is None else np.ascontiguousarray(g, dtype=f32).reshape(-1) for g in grays]
     used = np.zeros((V, rows * cols), dtype=np.uint8)
+    emitted = np.zeros((V, rows * cols), dtype=np.uint8)
     tally = collections.Counter({r: 0 for r in REASONS})
     yy, xx = np.mgrid[0:rows, 0:cols]
     xs, ys = xx.reshape(-1).astype(f32), yy.reshape(-1).astype(f32)
@@ -37,6 +39,10 @@ def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1
         tally["invalid"] += int((~val).sum())
         tally["used"] += int((val & (used[i] != 0)).sum())
         idx = np.nonzero(val & (used[i] == 0))[0]
+        if not len(idx):  # (every tally of a pair counts over idx: nothing to add, nothing to mark)
+            out.append(np.zeros(0, dtype=dmb._PLY_VERTEX))
+            per_view.append(0)
+            continue
         z = z_all[idx]
         n = [planes[i][idx, k] for k in range(3)]
         X = backproject(consts[i], z, xs[idx], ys[idx])
@@ -92,6 +98,8 @@ def fuse(norm4s, grays, consts, disp_thresh, cos_t, num_consistent, depth_min=-1
         v["red"] = v["green"] = v["blue"] = g
         for j, ok, q in hits:
             used[j][q[emit & ok]] = 1
+        emitted[i][idx[e]] = 1
         out.append(v)
         per_view.append(len(e))
-    return Result(np.concatenate(out), per_view, used.reshape(V, rows, cols), dict(tally))
+    return Result(np.concatenate(out), per_view, used.reshape(V, rows, cols), dict(tally),
+                  emitted.reshape(V, rows, cols))

@@ -2,7 +2,10 @@
 camera constants, the PLY writer, the CLI's folders and the C-ABI's argument checks.  GPU: the kernels equal the
 restatement in every bit, are deterministic, put fused points on the surface, and the batch runner's --fuse equals the
 CLI on the dumps."""
+import collections
+import contextlib
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -451,3 +454,422 @@ def test_fusion_removes_the_solver_outliers(hip, batch_scan):
     p_fused = np.percentile(_surface_distance(s, _xyz(fused)), 95)
     print("p95 distance to the surface: all per-view points %.3f, fused %.3f (%d points)" % (p_all, p_fused, len(fused)))
     assert p_fused < p_all
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the limits of the kernels and of the host loop ("limits pinned"): frames that do not fill their last
+# workgroup, more workgroups than one chunk of the scan, an output that outgrows its buffer, views that emit nothing,
+# 512 views, point ranges, a caller's stream.  Every scene is built once, restated once (tests/fusion_ref.py) and judged
+# by a condition function that says what the scene is there for -- checked on the restatement alone without a device,
+# and again by the GPU test that compares the kernels with it.
+# ----------------------------------------------------------------------------------------------------------------------
+WORKGROUP = 256  # fuse::kBlock: pixels per workgroup of evaluate_kernel / scatter_kernel
+SCAN_CHUNK = 1024  # fuse::kScan: workgroup counts per chunk of scan_kernel
+
+
+def _workgroups(npix):
+    return -(-npix // WORKGROUP)
+
+
+def _group_counts(mask):
+    """points per workgroup of one view's emitted mask"""
+    flat = mask.reshape(-1)
+    pad = np.zeros(_workgroups(flat.size) * WORKGROUP, dtype=np.int64)
+    pad[:flat.size] = flat
+    return pad.reshape(-1, WORKGROUP).sum(1)
+
+
+Case = collections.namedtuple("Case", "norm4s grays Ps cam_scale disp normal_thresh num_consistent ref")
+
+
+def _case(norm4s, grays, Ps, cam_scale, disp, normal_thresh, nc, depth=(300.0, 800.0)):
+    consts = [fusion.view_constants(P, cam_scale) for P in Ps]
+    ref = fusion_ref.fuse(norm4s, grays, consts, disp, fusion.cos_threshold(normal_thresh), nc, *depth)
+    return Case(norm4s, grays, Ps, cam_scale, disp, normal_thresh, nc, ref)
+
+
+@functools.lru_cache(maxsize=None)
+def _scan_case(n_views, cols, rows, seed, nc):
+    s = make_scan(n_views, cols, rows, seed)
+    return _case(s.norm4s, s.grays, s.Ps, s.cam_scale, 0.1 / s.cam_scale, 30.0, nc)
+
+
+def _fuse_case(c, **kw):
+    return fusion.fuse(c.norm4s, c.grays, c.Ps, c.cam_scale, c.disp, c.normal_thresh, c.num_consistent, 300.0, 800.0,
+                       return_info=True, **kw)
+
+
+def _assert_equals_ref(pts, per_view, used, ref, what):
+    """points, per-view counts and used masks in every byte; the message names the first record that differs"""
+    assert list(per_view) == ref.per_view, "%s: per_view %r, restated %r" % (what, list(per_view), ref.per_view)
+    if pts.tobytes() != ref.points.tobytes():
+        a, b = np.frombuffer(pts.tobytes(), np.uint8).reshape(-1, 27), np.frombuffer(ref.points.tobytes(), np.uint8).reshape(-1, 27)
+        k = int(np.nonzero((a != b).any(1))[0][0])
+        view = int(np.searchsorted(np.cumsum(ref.per_view), k, side="right"))
+        raise AssertionError("%s: %d of %d records differ, first at %d (view %d): %r, restated %r"
+                             % (what, int((a != b).any(1).sum()), len(a), k, view, pts[k], ref.points[k]))
+    bad = [v for v in range(len(ref.used)) if not np.array_equal(used[v], ref.used[v])]
+    assert not bad, "%s: the used masks of views %r differ" % (what, bad)
+
+
+# -- frames that do not fill their last workgroup ------------------------------------------------------------------------
+RAGGED = {  # name: (cols, rows, seed, range of rows * cols % 256, the last workgroup must hold emitted points)
+    "161x113": (161, 113, 41, (1, 63), True),     # 17 pixels in the last workgroup: one partial wavefront, three empty
+    "67x45": (67, 45, 42, (193, 255), True),      # 199: the last wavefront of the last workgroup is the partial one
+    "7x5": (7, 5, 43, (1, 63), False),            # less than one wavefront
+    "333x1": (333, 1, 44, (65, 127), False),      # a single row, two workgroups
+}
+
+
+def _ragged_case(name):
+    cols, rows, seed = RAGGED[name][:3]
+    return _scan_case(4, cols, rows, seed, 1)
+
+
+def _ragged_condition(name, ref):
+    cols, rows, _, (lo, hi), in_last = RAGGED[name]
+    npix = rows * cols
+    assert lo <= npix % WORKGROUP <= hi
+    assert sum(ref.per_view) > 0 and len(set(ref.per_view)) > 1
+    if in_last:  # points inside the last, partly filled workgroup -- and the workgroups differ in their counts
+        last = (_workgroups(npix) - 1) * WORKGROUP
+        assert ref.emitted[0].reshape(-1)[last:].any()
+        assert len(set(_group_counts(ref.emitted[0]))) > 1
+
+
+# -- more workgroups than one chunk of scan_kernel ---------------------------------------------------------------------
+CHUNKED = {  # name: (cols, rows, seed, workgroups, chunks)
+    "512x512": (512, 512, 51, 1024, 1),       # the chunk exactly full
+    "530x495": (530, 495, 52, 1025, 2),       # the second chunk: one workgroup, 206 pixels
+    "540x490": (540, 490, 53, 1034, 2),       # ten workgroups into the second chunk, the last with 152 pixels
+    "800x660": (800, 660, 54, 2063, 3),       # 528 000 pixels
+}
+
+
+def _chunked_case(name):
+    cols, rows, seed = CHUNKED[name][:3]
+    return _scan_case(3, cols, rows, seed, 1)
+
+
+def _chunked_condition(name, ref):
+    cols, rows, _, groups, chunks = CHUNKED[name]
+    npix = rows * cols
+    assert _workgroups(npix) == groups and -(-groups // SCAN_CHUNK) == chunks
+    counts = _group_counts(ref.emitted[0])
+    assert len(counts) == groups and len(set(counts)) > 1
+    for k in range(chunks):  # view 0 emits in every chunk: each carry is non-zero and each chunk's offsets are used
+        assert counts[k * SCAN_CHUNK:(k + 1) * SCAN_CHUNK].sum() > 0, (name, k)
+
+
+# -- an output that outgrows its buffer --------------------------------------------------------------------------------
+PAIR_DEPTHS = (400.0, 450.0, 500.0, 550.0, 600.0)
+
+
+@functools.lru_cache(maxsize=None)
+def _pairs_case(cols, rows):
+    """ten views in five pairs, all through one pinhole camera; both views of a pair see the fronto-parallel plane at the
+    pair's depth.  fb = 54.000004: neighbouring pairs are 0.008 .. 0.015 apart in disparity, disp_thresh is 0.005 -- a view
+    agrees with its partner only.  The first of a pair emits every pixel and marks every pixel of the second."""
+    P = _pinhole(100.0, cols / 2.0, rows / 2.0, np.eye(3), (0.0, 0.0, 0.0))
+    Ps = [P] * 10
+    n4s = _plane_views(Ps, [z for z in PAIR_DEPTHS for _ in (0, 1)], rows, cols)
+    yy, xx = np.mgrid[0:rows, 0:cols]
+    grays = [((xx * 3 + yy * 5 + 37 * (v // 2) + 11 * (v % 2)) % 200).astype(f32) for v in range(10)]
+    return _case(n4s, grays, Ps, 1.0, 0.005, 30.0, 1)
+
+
+def _pairs_condition(cols, rows, ref):
+    """capacity starts at npix: view 0 fills it exactly; views 2, 4 and 8 each need a larger buffer (2, 4, 8 npix)"""
+    npix = rows * cols
+    assert ref.per_view == [npix, 0] * 5 and sum(ref.per_view) == 5 * npix > 4 * npix
+    capacity, total, grown = npix, 0, []
+    for v, n in enumerate(ref.per_view):
+        if total + n > capacity:
+            grown.append(v)
+            while capacity < total + n:
+                capacity *= 2
+        total += n
+    assert grown == [2, 4, 8]
+    g = ref.points["red"].reshape(5, npix)  # the pairs' grays differ: a block in the wrong place cannot compare equal
+    assert all(not np.array_equal(g[a], g[b]) for a in range(5) for b in range(a))
+    assert [ref.used[v].all() for v in range(10)] == [False, True] * 5
+
+
+# -- views that emit nothing -------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _silent_case(which):
+    """three views of the plane Z = 500 through one camera.  "normal": normal_thresh = 0, cos_t = 1.0 and no n . n' > 1;
+    "count": num_consistent = 3 with two partners"""
+    P = _pinhole(100.0, 20.0, 15.0, np.eye(3), (0.0, 0.0, 0.0))
+    n4s = _plane_views([P] * 3, [500.0] * 3, 30, 40)
+    grays = [np.full((30, 40), 10.0 * v, dtype=f32) for v in range(3)]
+    return _case(n4s, grays, [P] * 3, 1.0, 0.1, 0.0 if which == "normal" else 30.0, 1 if which == "normal" else 3)
+
+
+def _silent_condition(which, ref):
+    assert ref.per_view == [0, 0, 0] and len(ref.points) == 0 and not ref.used.any() and not ref.emitted.any()
+    if which == "normal":
+        assert fusion.cos_threshold(0.0) == f32(1.0) and ref.tally["normal"] == 3 * 2 * 1200 and ref.tally["too_few"] == 3 * 1200
+    else:
+        assert ref.tally["normal"] == 0 and ref.tally["too_few"] == 3 * 1200
+
+
+# -- many views --------------------------------------------------------------------------------------------------------
+MANY = {100: (24, 18), 512: (13, 9)}  # views: (cols, rows)
+
+
+@functools.lru_cache(maxsize=None)
+def _many_case(V):
+    """V pinhole cameras (f = 100) translated along x in steps of 0.02, all seeing the plane Z = 500: 0.004 pixels of
+    disparity per step.  With 100 views every partner pixel is the pixel itself; with 512 the partner is up to two
+    columns away, and the columns that no earlier view reaches are emitted by later views."""
+    cols, rows = MANY[V]
+    Ps = [_pinhole(100.0, cols / 2.0, rows / 2.0, np.eye(3), (0.02 * k, 0.0, 0.0)) for k in range(V)]
+    n4s = _plane_views(Ps, [500.0] * V, rows, cols)
+    yy, xx = np.mgrid[0:rows, 0:cols]
+    grays = [((xx * 7 + yy * 13 + v * 3) % 256).astype(f32) for v in range(V)]
+    return _case(n4s, grays, Ps, 1.0, 0.05, 30.0, 3)
+
+
+def _many_condition(V, ref):
+    cols, rows = MANY[V]
+    assert len(ref.per_view) == V
+    if V == 100:
+        assert ref.per_view == [cols * rows] + [0] * 99
+    else:
+        assert V == abi.FUSION_MAX_VIEWS
+        assert sum(ref.per_view) == 153 and ref.per_view[0] == cols * rows and max(np.nonzero(ref.per_view)[0]) >= 256
+    assert all(u.any() for u in ref.used[1:])  # view 0 marked a pixel in every other view: all V - 1 passed the tests
+
+
+@functools.lru_cache(maxsize=None)
+def _dtu40_case():
+    """40 views of DTU geometry (beyond the solver's 32): _dtu_views repeats cameras when asked for more than the scan's
+    selection holds, each repeat with damage of its own"""
+    return _scan_case(40, 80, 60, 61, 3)
+
+
+def _dtu40_condition(ref):
+    assert len(ref.per_view) == 40 > abi.MAX_VIEWS and sum(1 for n in ref.per_view if n) >= 8
+    assert all(ref.tally[r] > 0 for r in fusion_ref.REASONS if r != "behind"), ref.tally
+
+
+# -- CPU: each scene reaches what it is there for ----------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(RAGGED))
+def test_ragged_scenes_emit_in_their_last_workgroup(name):
+    _ragged_condition(name, _ragged_case(name).ref)
+
+
+@pytest.mark.parametrize("name", sorted(CHUNKED))
+def test_chunked_scenes_emit_in_every_chunk_of_the_scan(name):
+    _chunked_condition(name, _chunked_case(name).ref)
+
+
+@pytest.mark.parametrize("cols,rows", [(67, 45)])
+def test_pairs_scene_outgrows_the_point_buffer_three_times(cols, rows):
+    _pairs_condition(cols, rows, _pairs_case(cols, rows).ref)
+
+
+@pytest.mark.parametrize("which", ["normal", "count"])
+def test_silent_scenes_emit_nothing(which):
+    _silent_condition(which, _silent_case(which).ref)
+
+
+@pytest.mark.parametrize("V", sorted(MANY))
+def test_many_view_scenes_reach_every_view(V):
+    _many_condition(V, _many_case(V).ref)
+
+
+def test_forty_dtu_views_scene_reaches_the_contract_s_branches():
+    _dtu40_condition(_dtu40_case().ref)
+
+
+def test_the_restatement_s_emitted_mask_counts_the_points_in_scan_order():
+    ref = _ragged_case("67x45").ref
+    assert [int(e.sum()) for e in ref.emitted] == ref.per_view
+    assert ref.emitted.dtype == np.uint8 and ref.emitted.shape == ref.used.shape and set(np.unique(ref.emitted)) == {0, 1}
+    # a view that finds no valid unused pixel (every second one of the pairs scene) leaves without a record or a tally
+    pairs = _pairs_case(67, 45).ref
+    assert [int(e.sum()) for e in pairs.emitted] == pairs.per_view and pairs.tally["used"] == 5 * 67 * 45
+
+
+def test_513_views_are_refused():
+    lib = abi.load_library()
+    assert abi.FUSION_MAX_VIEWS == 512
+    assert "#define GIPUMA_HIP_FUSION_MAX_VIEWS 512" in open(os.path.join(ROOT, "include", "gipuma_hip.h")).read()
+    host = np.zeros((4, 4, 4), dtype=f32)
+    views = (abi.FusionView * 513)()
+    for v in views:
+        v.norm4 = host.ctypes.data
+    h = C.c_void_p()
+    assert lib.gipuma_hip_fuse(C.byref(_desc(views, 513)), C.byref(h)) == abi.ERR_ARG and not h.value
+    assert b"512" in lib.gipuma_hip_last_error()
+    with pytest.raises(ValueError, match="2..512 views"):
+        fusion.fuse([host] * 513, [None] * 513, [np.eye(3, 4)] * 513)
+
+
+# -- GPU ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(RAGGED))
+def test_ragged_frames_equal_the_restatement(hip, name):
+    """pix < npix false in the last workgroup, a last wavefront partly outside the frame, workgroups without a pixel in
+    three of their wavefronts, a frame below one wavefront, a single row"""
+    c = _ragged_case(name)
+    _ragged_condition(name, c.ref)
+    pts, info = _fuse_case(c)
+    _assert_equals_ref(pts, info["per_view"], info["used"], c.ref, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CHUNKED))
+def test_scan_chunks_equal_the_restatement(hip, name):
+    """1024, 1025, 1034 and 2063 workgroups: scan_kernel's carry over one, two and three chunks of 1024 counts"""
+    c = _chunked_case(name)
+    _chunked_condition(name, c.ref)
+    pts, info = _fuse_case(c)
+    _assert_equals_ref(pts, info["per_view"], info["used"], c.ref, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cols,rows", [(67, 45)])
+def test_growing_the_point_buffer_keeps_the_earlier_views_points(hip, cols, rows):
+    """five times a frame's worth of points: the buffer is grown at the third, fifth and ninth view; every second view
+    emits nothing and its scatter is skipped"""
+    c = _pairs_case(cols, rows)
+    _pairs_condition(cols, rows, c.ref)
+    pts, info = _fuse_case(c)
+    _assert_equals_ref(pts, info["per_view"], info["used"], c.ref, "pairs %dx%d" % (cols, rows))
+    assert len(pts) == 5 * rows * cols
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["normal", "count"])
+def test_views_that_emit_nothing_give_an_empty_cloud(hip, which):
+    c = _silent_case(which)
+    _silent_condition(which, c.ref)
+    pts, info = _fuse_case(c)
+    assert len(pts) == 0 and pts.dtype == dmb._PLY_VERTEX and info["per_view"] == [0, 0, 0] and not info["used"].any()
+    _assert_equals_ref(pts, info["per_view"], info["used"], c.ref, which)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V", sorted(MANY))
+def test_many_views_equal_the_restatement(hip, V):
+    """100 and 512 (the header's limit) views: the view table beyond a handful of entries, used planes up to
+    511 * npix + pix.  The 512-view call is about 1500 launches and 512 stream waits on a 117-pixel frame; its time on
+    an MI355X has not been measured yet (the restatement takes 0.6 s)"""
+    c = _many_case(V)
+    _many_condition(V, c.ref)
+    pts, info = _fuse_case(c)
+    _assert_equals_ref(pts, info["per_view"], info["used"], c.ref, "%d views" % V)
+
+
+@pytest.mark.gpu
+def test_forty_dtu_views_equal_the_restatement(hip):
+    c = _dtu40_case()
+    _dtu40_condition(c.ref)
+    pts, info = _fuse_case(c)
+    _assert_equals_ref(pts, info["per_view"], info["used"], c.ref, "40 DTU views")
+
+
+@contextlib.contextmanager
+def _fused(lib, c, stream=None, planes=None):
+    """gipuma_hip_fuse through the C-ABI, the descriptor built as fusion.fuse builds it, the handle kept: yields
+    (handle, number of points).  stream: a torch stream whose handle goes into desc.stream -- then `planes` (norm4, gray
+    device tensors written on that stream) are passed as they are and nothing is synchronised before the call."""
+    dev, keep = torch.device("cuda", 0), []
+    V = len(c.norm4s)
+    n4s, grays = planes if planes is not None else (c.norm4s, c.grays)
+    views = (abi.FusionView * V)()
+    for v in range(V):
+        abi.fill_view(views[v], fusion.view_constants(c.Ps[v], c.cam_scale), abi.device_plane(n4s[v], dev, keep),
+                      abi.device_plane(grays[v], dev, keep) if grays[v] is not None else None)
+    d = abi.FusionDesc()
+    d.abi_version = abi.ABI_VERSION
+    d.rows, d.cols, d.n_views = c.norm4s[0].shape[0], c.norm4s[0].shape[1], V
+    d.views = C.cast(views, C.POINTER(abi.FusionView))
+    d.disp_thresh, d.normal_thresh, d.num_consistent = c.disp, c.normal_thresh, c.num_consistent
+    d.depth_min, d.depth_max, d.device_id = 300.0, 800.0, 0
+    if stream is None:
+        torch.cuda.synchronize(dev)
+    else:
+        assert stream.cuda_stream
+        d.stream = stream.cuda_stream
+    h = C.c_void_p()
+    abi.check(lib, lib.gipuma_hip_fuse(C.byref(d), C.byref(h)), "gipuma_hip_fuse")
+    try:
+        n = C.c_int64()
+        abi.check(lib, lib.gipuma_hip_fusion_count(h, C.byref(n), None, None), "gipuma_hip_fusion_count")
+        yield h, n.value
+    finally:
+        lib.gipuma_hip_fusion_free(h)
+
+
+def _read(lib, h, first, count):
+    out = np.zeros(count, dtype=dmb._PLY_VERTEX)
+    abi.check(lib, lib.gipuma_hip_fusion_points(h, out.ctypes.data, first, count), "gipuma_hip_fusion_points")
+    return out
+
+
+def _results(lib, h, n, V, rows, cols):
+    per_view, used = (C.c_int64 * V)(), np.empty((V, rows, cols), dtype=np.uint8)
+    abi.check(lib, lib.gipuma_hip_fusion_count(h, None, per_view, None), "gipuma_hip_fusion_count")
+    abi.check(lib, lib.gipuma_hip_fusion_used(h, used.ctypes.data), "gipuma_hip_fusion_used")
+    return _read(lib, h, 0, n), list(per_view), used
+
+
+@pytest.mark.gpu
+def test_point_ranges_read_the_same_records_and_check_their_bounds(hip):
+    lib = hip
+    c = _ragged_case("67x45")
+    with _fused(lib, c) as (h, n):
+        whole = _read(lib, h, 0, n)
+        assert n == len(c.ref.points) > 100 and whole.tobytes() == c.ref.points.tobytes()
+        a, b = n // 7, n // 7 + (2 * n) // 3  # three uneven pieces
+        pieces = [_read(lib, h, 0, a), _read(lib, h, a, b - a), _read(lib, h, b, n - b)]
+        assert 0 < a < b < n and len({len(p) for p in pieces}) == 3
+        assert np.concatenate(pieces).tobytes() == whole.tobytes()
+        for k in (0, 1, 2, n - 3, n - 2, n - 1):  # record by record at both ends
+            assert _read(lib, h, k, 1).tobytes() == whole[k:k + 1].tobytes(), k
+        points = lib.gipuma_hip_fusion_points
+        for first in (0, 1, n - 1, n):  # nothing to read: no destination needed, the end itself is a valid start
+            assert points(h, None, first, 0) == 0
+        assert points(h, None, 0, 1) == abi.ERR_ARG
+        spare = np.zeros(4, dtype=dmb._PLY_VERTEX)
+        int64_max = (1 << 63) - 1
+        for first, count in ((-1, 1), (-1, 0), (0, -1), (n - 1, 2), (n, 1), (0, n + 1), (n + 1, 0), (int64_max, 1),
+                             (int64_max, 0), (1, int64_max)):
+            assert points(h, spare.ctypes.data, first, count) == abi.ERR_ARG, (first, count)
+            assert b"out of bounds" in lib.gipuma_hip_last_error()
+        assert not spare.tobytes().strip(b"\0")  # ... and nothing was written
+        assert points(None, spare.ctypes.data, 0, 1) == abi.ERR_ARG
+        assert lib.gipuma_hip_fusion_count(h, None, None, None) == 0
+        assert lib.gipuma_hip_fusion_count(None, None, None, None) == abi.ERR_ARG
+    with _fused(lib, _silent_case("normal")) as (h, n):  # an empty cloud: the only valid range is (0, 0)
+        assert n == 0 and lib.gipuma_hip_fusion_points(h, None, 0, 0) == 0
+        assert lib.gipuma_hip_fusion_points(h, spare.ctypes.data, 0, 1) == abi.ERR_ARG
+        assert lib.gipuma_hip_fusion_points(h, None, 1, 0) == abi.ERR_ARG
+
+
+@pytest.mark.gpu
+def test_fusion_on_a_caller_s_stream(hip):
+    """desc.stream = a torch stream on which the planes were written just before, the device not synchronised: the library
+    runs behind them on that stream.  Two frame sizes one after the other on the same stream; each equals the restatement
+    and the call on a stream of the library's own"""
+    lib = hip
+    stream = torch.cuda.Stream()
+    assert stream.cuda_stream != 0 and torch.cuda.current_stream().cuda_stream == 0
+    for name in ("161x113", "67x45"):
+        c = _ragged_case(name)
+        V, (rows, cols) = len(c.norm4s), c.norm4s[0].shape[:2]
+        staged = [torch.from_numpy(n).cuda() for n in c.norm4s], [torch.from_numpy(g).cuda() for g in c.grays]
+        torch.cuda.synchronize()
+        with torch.cuda.stream(stream):  # the planes the library reads: device copies queued on the caller's stream
+            planes = [t.clone() for t in staged[0]], [t.clone() for t in staged[1]]
+        with _fused(lib, c, stream, planes) as (h, n):
+            on_stream = _results(lib, h, n, V, rows, cols)
+        with _fused(lib, c) as (h, n):
+            default = _results(lib, h, n, V, rows, cols)
+        _assert_equals_ref(*on_stream, c.ref, "%s on the caller's stream" % name)
+        _assert_equals_ref(*default, c.ref, "%s on the library's stream" % name)
+        assert on_stream[0].tobytes() == default[0].tobytes()

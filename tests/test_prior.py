@@ -8,6 +8,7 @@ import functools
 import json
 import os
 import subprocess
+import sys
 import tempfile
 
 import numpy as np
@@ -385,6 +386,115 @@ def test_prior_equals_the_restatement_bit_for_bit(hip, name, cols, rows, n_src, 
         assert ref.info["grazing"][ref.info["cls"] != 2].all() and ref.counts[1] == 0
     if S == 32:  # the second and later passes over the views repeat maps bit for bit: the lower ordinal wins the ties
         assert (ref.info["source"] >= 4).any() and not ((ref.info["source"] >= 8) & (ref.info["source"] < 31)).any()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# GPU: a caller's stream (desc.stream was NULL in every call above: torch's default stream has the handle 0)
+# ----------------------------------------------------------------------------------------------------------------------
+STREAM_FRAMES = [(96, 64), (161, 113)]  # (cols, rows) of the two calls queued back to back: the second is the larger
+
+
+@functools.lru_cache(maxsize=None)
+def _stream_case(cols, rows):
+    """4 perturbed sources of the scan at this size and the restated prior (default knobs, depth 300..800)"""
+    scan = _scan(cols, rows, 4)
+    n4s, Ps, _ = _perturbed_sources(scan, 4, seed=cols + 4)
+    ref = prior_ref.prior_from_views(fusion.view_constants(scan.P_matrices[0], scan.cam_scale), n4s,
+                                     [fusion.view_constants(P, scan.cam_scale) for P in Ps], 300.0, 800.0)
+    return scan, n4s, Ps, ref
+
+
+def _stream_condition(ref, rows, cols):
+    """direct, filled and empty pixels, several sources among the winners, both outcomes of the grazing guard"""
+    assert sum(ref.counts) == rows * cols and all(n > 0 for n in ref.counts), ref.counts
+    assert len(np.unique(ref.info["source"][ref.info["cls"] != 2])) >= 3
+    assert ref.info["grazing"].any() and not ref.info["grazing"][ref.info["cls"] != 2].all()
+
+
+def test_the_stream_cases_reach_every_class_and_the_second_frame_is_the_larger():
+    (c0, r0), (c1, r1) = STREAM_FRAMES
+    assert c0 * r0 < c1 * r1 and (c1 * r1) % 256 == 17  # grows the key plane; a ragged last workgroup
+    for cols, rows in STREAM_FRAMES:
+        _stream_condition(_stream_case(cols, rows)[3], rows, cols)
+
+
+# The child of test_prior_enqueued_twice_on_a_caller_s_stream: a fresh process, so the device's cached key plane starts
+# empty whatever ran before, and the second call must replace it.  argv: the .npz of the inputs, the .npz to write.
+_STREAM_CHILD = r"""
+import sys
+import numpy as np
+import torch
+from gipuma_amd import abi, prior, pyramid
+src, dst = sys.argv[1:3]
+data = np.load(src)
+assert abi.load_library().gipuma_hip_device_count() >= 1
+stream = torch.cuda.Stream()
+assert stream.cuda_stream != 0
+staged = [[torch.from_numpy(data["n4_%d_%d" % (c, k)]).cuda() for k in range(4)] for c in (0, 1)]
+busy = torch.zeros(1 << 26, dtype=torch.float32, device="cuda:0")
+pyramid.downsample(torch.zeros(4, 4, device="cuda:0"))  # the library's kernels are loaded; the prior's scratch is untouched
+torch.cuda.synchronize()
+outs, queued = [], []
+with torch.cuda.stream(stream):
+    for _ in range(400):  # device work ahead of the calls: the first has not run when the second is made
+        busy.add_(1.0)
+    for c in (0, 1):
+        planes = [t.clone() for t in staged[c]]  # the sources: written on this stream, after the work above
+        outs.append(prior.prior_from_views(data["P_target_%d" % c], planes, list(data["Ps_%d" % c]), float(data["cam_scale_%d" % c]),
+                                           300.0, 800.0))
+        queued.append(not stream.query())
+    stream.synchronize()
+np.savez(dst, queued=queued, busy=float(busy[0].item()), out_0=outs[0].cpu().numpy(), out_1=outs[1].cpu().numpy())
+"""
+
+
+@pytest.mark.gpu
+def test_prior_enqueued_twice_on_a_caller_s_stream(hip, tmp_path):
+    """without counts or time the call only enqueues: two calls back to back on one non-default stream, 96x64 then 161x113
+    -- the second replaces the cached key plane while the first is still queued -- synchronised once after both; both
+    priors equal the restatement in every bit.  In a child process: the cache of this one only grows, and an earlier
+    test's 1600x1200 frame would keep the second call from growing it"""
+    src, dst = str(tmp_path / "in.npz"), str(tmp_path / "out.npz")
+    arrays, refs = {}, []
+    for c, (cols, rows) in enumerate(STREAM_FRAMES):
+        scan, n4s, Ps, ref = _stream_case(cols, rows)
+        _stream_condition(ref, rows, cols)
+        refs.append(ref)
+        arrays.update({"n4_%d_%d" % (c, k): n4s[k] for k in range(4)})
+        arrays.update({"P_target_%d" % c: np.asarray(scan.P_matrices[0]), "Ps_%d" % c: np.stack([np.asarray(P) for P in Ps]),
+                       "cam_scale_%d" % c: np.float64(scan.cam_scale)})
+    np.savez(src, **arrays)
+    subprocess.run([sys.executable, "-c", _STREAM_CHILD, src, dst], cwd=ROOT, check=True, timeout=300)
+    got = np.load(dst)
+    assert got["busy"] == 400.0
+    # the first call returned with the stream still busy: it enqueued and did not synchronise.  (Nothing of the kind holds
+    # after the second: releasing the smaller key plane waits for the device.)
+    assert bool(got["queued"][0])
+    for c, (cols, rows) in enumerate(STREAM_FRAMES):
+        assert_same(got["out_%d" % c], refs[c].prior, "call %d (%dx%d) on the caller's stream" % (c, cols, rows))
+
+
+@pytest.mark.gpu
+def test_prior_with_counts_on_a_caller_s_stream_has_completed(hip):
+    """return_info on a non-default stream: the library synchronises that stream for the counts, so counts and plane are
+    the restatement's as soon as the call returns; once more without (enqueue only), read after synchronising"""
+    torch = _torch()
+    cols, rows = STREAM_FRAMES[1]
+    scan, n4s, Ps, ref = _stream_case(cols, rows)
+    _stream_condition(ref, rows, cols)
+    stream = torch.cuda.Stream()
+    assert stream.cuda_stream != 0
+    staged = [torch.from_numpy(n).cuda() for n in n4s]
+    torch.cuda.synchronize()
+    with torch.cuda.stream(stream):
+        planes = [t.clone() for t in staged]
+        got, info = prior.prior_from_views(scan.P_matrices[0], planes, Ps, scan.cam_scale, 300.0, 800.0, return_info=True)
+        assert stream.query()  # nothing left in flight
+        assert [info["direct"], info["filled"], info["empty"]] == ref.counts and info["device_ms"] > 0
+        again = prior.prior_from_views(scan.P_matrices[0], planes, Ps, scan.cam_scale, 300.0, 800.0)
+    stream.synchronize()
+    assert_same(got.cpu().numpy(), ref.prior, "prior with counts on the caller's stream")
+    assert_same(again.cpu().numpy(), ref.prior, "prior enqueued on the caller's stream")
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -170,6 +170,32 @@ def test_downsample_two_levels_in_a_row_and_float_planes(hip):
         assert_same(pyr.planes[2][0].cpu().numpy(), pyramid_ref.downsample2(r1), "ScanPyramid level 2")
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows,cols,channels", [(37, 45, 1), (21, 33, 4)])
+def test_downsample_on_a_caller_s_stream(hip, rows, cols, channels):
+    """a non-default stream (every call above ran on torch's default stream, whose handle is 0): the source is written on
+    that stream just before the call, the call does not synchronise, and the level equals the restatement once the stream
+    is complete.  Odd rows and columns, gray and colour"""
+    torch = _torch()
+    assert rows % 2 == 1 and cols % 2 == 1
+    rng = np.random.default_rng(rows * 17 + cols)
+    host = rng.integers(0, 256, size=(rows, cols) + ((4,) if channels == 4 else ())).astype(f32)
+    stream = torch.cuda.Stream()
+    assert stream.cuda_stream != 0 and torch.cuda.current_stream().cuda_stream == 0
+    staged = torch.from_numpy(host).cuda()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(stream):
+        assert torch.cuda.current_stream().cuda_stream == stream.cuda_stream
+        src = torch.full_like(staged, -9.0)
+        src.copy_(staged)  # the write the kernel has to run behind
+        got = pyramid.downsample(src)
+        again = pyramid.downsample(src, out=torch.full_like(got, -1.0))
+    stream.synchronize()
+    want = pyramid_ref.downsample2(host)
+    assert_same(got.cpu().numpy(), want, "downsample %dx%d ch %d on a caller's stream" % (cols, rows, channels))
+    assert_same(again.cpu().numpy(), want, "downsample into a plane filled on that stream")
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # GPU: the seed
 # ------------------------------------------------------------------------------------------------------------------
