@@ -122,6 +122,15 @@ class PriorDesc(C.Structure):
     ]
 
 
+class CloudDesc(C.Structure):
+    """gipuma_hip_cloud_desc: two device clouds of packed float32 xyz, the search radius and the grid (0: automatic)"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("n_queries", C.c_int64), ("n_targets", C.c_int64), ("queries", C.c_void_p),
+        ("targets", C.c_void_p), ("max_dist", C.c_float), ("grid", C.c_int32), ("device_id", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 # every symbol include/gipuma_hip.h declares: (name, restype, argtypes)
 _FP = C.POINTER(C.c_float)
 SYMBOLS = [
@@ -155,6 +164,8 @@ SYMBOLS = [
     ("gipuma_hip_fusion_used", C.c_int, [C.c_void_p, C.c_void_p]),
     ("gipuma_hip_fusion_free", C.c_int, [C.c_void_p]),
     ("gipuma_hip_prior_from_views", C.c_int, [C.POINTER(PriorDesc), C.c_void_p, C.POINTER(C.c_int64), _FP]),
+    ("gipuma_hip_cloud_nearest", C.c_int, [C.POINTER(CloudDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), _FP]),
+    ("gipuma_hip_cloud_last_stats", C.c_int, [C.POINTER(C.c_int64)]),
 ]
 
 _lib = None

@@ -30,7 +30,10 @@ MI355X-first differences from the shell loop:
   * --fuse: the results of this run are also fused on the GPU, from memory, into <output>/fused.ply (with
     --disp_thresh / --normal_thresh / --num_consistent and the depth range) -- what the reference's
     scripts leave to an external CUDA tool after the loop (scripts/dtu_fast.sh:56-57).  One process only: with
-    WORLD_SIZE > 1 run `python -m gipuma_amd.fusion` on the output folder instead.
+    WORLD_SIZE > 1 run `python -m gipuma_amd.fusion` on the output folder instead;
+  * --eval_cloud gt.ply (with --fuse): the fused cloud is scored against that reference cloud on the GPU -- accuracy,
+    completeness, precision / recall / F-score within --eval_max_dist (gipuma_amd.cloud_eval) -- and the
+    score joins the report as `cloud_score`.
 
 Images: what the reference's scripts hand to imread (main.cpp:739-751) -- PNG, JPG (through PIL), binary PGM / PPM.
 Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
@@ -312,11 +315,19 @@ def parse_args(argv):
     pa.add_argument("--disp_thresh", type=float, default=0.1, help="with --fuse")
     pa.add_argument("--normal_thresh", type=float, default=30.0, help="with --fuse, degrees")
     pa.add_argument("--num_consistent", type=int, default=3, help="with --fuse")
+    pa.add_argument("--eval_cloud", default=None,
+                    help="with --fuse: a reference cloud (PLY) to score the fused cloud against (gipuma_amd.cloud_eval)")
+    pa.add_argument("--eval_max_dist", type=float, default=20.0,
+                    help="with --eval_cloud: distances beyond it are discarded")
     args = pa.parse_args(argv)
     # the reference parses these with sscanf("%f") into float fields (main.cpp:300-360)
     for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
-              "normal_thresh"):
+              "normal_thresh", "eval_max_dist"):
         setattr(args, k, float(np.float32(getattr(args, k))))
+    if args.eval_cloud is not None and not args.fuse:
+        pa.error("--eval_cloud scores the fused cloud: it needs --fuse")
+    if args.eval_cloud is not None and not (args.eval_max_dist > 0 and np.isfinite(args.eval_max_dist)):
+        pa.error("--eval_max_dist must be > 0 and finite")
     if args.levels < 1:
         raise SystemExit("--levels must be >= 1")
     args.level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
@@ -352,11 +363,22 @@ def fuse_solved(scan):
                                args.normal_thresh, args.num_consistent, args.depth_min, args.depth_max,
                                device_id=scan.dev[0].device.index, return_info=True)
     dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
+    scan.fused_xyz = np.stack([points["x"], points["y"], points["z"]], axis=-1)  # (for --eval_cloud)
     return {"points": int(len(points)), "device_ms": info["device_ms"],
             "views": [{"name": n, "emitted": int(c)} for n, c in zip(fused_views, info["per_view"])]}
 
 
-def write_report(scan, head, pyr, order, fused):
+def score_fused(scan):
+    """--eval_cloud: the fused cloud of this run against the reference cloud; returns the report's `cloud_score`"""
+    from . import cloud_eval
+    args = scan.args
+    out = cloud_eval.score(scan.fused_xyz, dmb.read_ply_xyz(args.eval_cloud), args.eval_max_dist,
+                           device_id=scan.dev[0].device.index)
+    out["reference"] = args.eval_cloud
+    return out
+
+
+def write_report(scan, head, pyr, order, fused, cloud_score=None):
     """batch_rank<rank>.json: `head`, the options of the strategy that ran, the throughput and the per-view entries"""
     args, t_batch = scan.args, head["batch_seconds"]
     n_done = sum(1 for r in scan.report if "skipped" not in r)
@@ -367,7 +389,8 @@ def write_report(scan, head, pyr, order, fused):
                "prior_min_views": args.prior_min_views, "prior_max_cost": args.prior_max_cost, "order": order}
               if args.view_prior else {}),
            "mpix_per_s_batch": n_done * scan.rows * scan.cols / max(t_batch, 1e-9) / 1e6,
-           "views": scan.report, **({"fusion": fused} if fused is not None else {})}
+           "views": scan.report, **({"fusion": fused} if fused is not None else {}),
+           **({"cloud_score": cloud_score} if cloud_score is not None else {})}
     with open(os.path.join(args.output_folder, "batch_rank%d.json" % head["rank"]), "w") as f:
         json.dump(out, f, indent=1)
 
@@ -408,8 +431,10 @@ def main(argv=None):
         # uses them)
         abi.load_library().gipuma_hip_cache_clear()
     t_batch = time.perf_counter() - t_batch0
+    fused = fuse_solved(scan) if args.fuse else None
     write_report(scan, {"rank": rank, "world": world, "device": dev_index, "load_seconds": scan.load_seconds,
-                        "in_flight": in_flight, "batch_seconds": t_batch}, pyr, order, fuse_solved(scan) if args.fuse else None)
+                        "in_flight": in_flight, "batch_seconds": t_batch}, pyr, order, fused,
+                 score_fused(scan) if args.eval_cloud is not None else None)
     print("rank %d/%d: %d reference views on cuda:%d" % (rank, world, len(scan.report), dev_index))
     return 0
 

@@ -1,0 +1,492 @@
+// gipuma_cloud.hip -- nearest neighbours between two point clouds on gfx950: the search behind the cloud-against-cloud
+// score (accuracy / completeness).
+//
+// The contract (include/gipuma_hip.h) is restated on the CPU in numpy float32 by tests/cloud_ref.py as a
+// brute-force search.  For query a and target b, float32 without contraction (-ffp-contract=off):
+//     dx = a.x - b.x;  dy = a.y - b.y;  dz = a.z - b.z;  d2 = (dx*dx + dy*dy) + dz*dz
+//     b is a candidate iff it is finite and d2 <= r2 (r2 = max_dist * max_dist);  the answer is the smallest (d2, j).
+// A minimum over (d2, j) pairs does not depend on the order the candidates are visited in, so a uniform grid over the
+// targets may prune the search as long as it never skips a target the brute force would accept or prefer: the result
+// then equals the brute force in every bit.  Why each shortcut keeps that promise is written where it is taken
+// (cell_of, the box early-out in count_kernel, the shell stop in search_kernel).
+//
+// Launches, all on one stream:
+//   cloud::box_partial_kernel / box_final_kernel   bounding box of the finite targets, a two-stage min / max reduction
+//                                                  (no float atomics); the host reads the 24 bytes and lays the grid out
+//   cloud::count_kernel<false>, scan_kernel, scatter_kernel    counting sort of the targets by cell: histogram, exclusive
+//                                                  scan over the cells (one workgroup, carry across chunks), scatter
+//   cloud::count_kernel<true>, scan_kernel, scatter_kernel     the same for the queries, so that the lanes of a wavefront
+//                                                  visit the same cells; a query that is not finite or lies farther than
+//                                                  max_dist from the targets' box is answered "none" here and not sorted
+//   cloud::search_kernel                           one lane per sorted query: shells of growing Chebyshev distance around
+//                                                  its cell; the result goes to the query's original index
+// The histogram and the scatter use integer atomics (as the prior's z-buffer does), so the order of the points INSIDE a
+// cell varies from run to run.  The contract's result does not depend on that order: the search carries (d2, j) compared
+// lexicographically, and a cell's points are all visited or all skipped.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "pm_host.h"
+
+using pm_host::fail;
+
+namespace cloud {
+
+constexpr int kBlock = 256;        // points per workgroup: 4 wavefronts
+constexpr int kScan = 1024;        // threads of the scan workgroup
+constexpr int kItems = 16;         // cells per thread and chunk of the scan: a chunk is 16384 cells
+constexpr int kBoxBlocks = 1024;   // workgroups (at most) of the first box stage
+constexpr int kMaxGrid = 256;      // cells along the longest axis: at most 2^24 cells
+enum { kEarly = 0, kSearched = 1, kFound = 2, kTargets = 3, kStats = 4 };  // the device counters
+
+struct Grid {
+    float lo[3], hi[3];  // bounding box of the finite targets
+    float h, inv_h;      // cell edge, 1 / h
+    float r2;            // max_dist^2
+    int g[3];            // cells per axis, 1 .. kMaxGrid
+};
+
+struct __align__(16) Rec {  // a sorted point: its coordinates and its index in the caller's array
+    float x, y, z;
+    int32_t j;
+};
+
+// The cell of coordinate p along an axis with g cells: clamp(floor((p - lo) * inv_h), 0, g - 1).  p - lo, the product
+// with inv_h > 0, floorf, the clamp and the conversion are each non-decreasing in p, so cell_of is MONOTONIC in p; the
+// search relies on nothing else about it.  (Clamped as a float, before the conversion: a query far outside the box may
+// give +-inf here, never NaN -- p and lo are finite, inv_h is finite and > 0.)  The clamp is what places a query outside
+// the box: in the nearest cell of the border, which keeps the monotonicity.
+__device__ __forceinline__ int cell_of(float p, float lo, float inv_h, int g)
+{
+    if (g == 1) return 0;
+    const float t = floorf((p - lo) * inv_h);
+    return (int)fminf(fmaxf(t, 0.f), (float)(g - 1));
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// min of lo[3] / max of hi[3] over the workgroup, left in lane 0's m[]
+__device__ __forceinline__ void reduce_box(float (*s)[kBlock], float m[6])
+{
+    const int t = threadIdx.x;
+    for (int k = 0; k < 6; ++k) s[k][t] = m[k];
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if (t < off)
+            for (int k = 0; k < 6; ++k) s[k][t] = k < 3 ? fminf(s[k][t], s[k][t + off]) : fmaxf(s[k][t], s[k][t + off]);
+        __syncthreads();
+    }
+    for (int k = 0; k < 6; ++k) m[k] = s[k][0];
+}
+
+// per workgroup: (lo, hi) of its finite points; +inf / -inf where it has none
+__global__ __launch_bounds__(kBlock) void box_partial_kernel(const float *__restrict__ pts, uint32_t n, float *__restrict__ partial)
+{
+    __shared__ float s[6][kBlock];
+    float m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {  // (n < 2^31: i does not wrap)
+        const float *p = pts + 3 * (size_t)i;
+        const float x = p[0], y = p[1], z = p[2];
+        if (!finite3(x, y, z)) continue;
+        m[0] = fminf(m[0], x);
+        m[1] = fminf(m[1], y);
+        m[2] = fminf(m[2], z);
+        m[3] = fmaxf(m[3], x);
+        m[4] = fmaxf(m[4], y);
+        m[5] = fmaxf(m[5], z);
+    }
+    reduce_box(s, m);
+    if (threadIdx.x < 6) partial[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(kBlock) void box_final_kernel(const float *__restrict__ partial, int nblocks, float *__restrict__ box)
+{
+    __shared__ float s[6][kBlock];
+    float m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (int b = threadIdx.x; b < nblocks; b += kBlock)
+        for (int k = 0; k < 6; ++k) m[k] = k < 3 ? fminf(m[k], partial[b * 6 + k]) : fmaxf(m[k], partial[b * 6 + k]);
+    reduce_box(s, m);
+    if (threadIdx.x < 6) box[threadIdx.x] = s[threadIdx.x][0];
+}
+
+// The histogram: cellid[i] = the point's cell, or -1 for a point that takes no part; counts[cell] += 1.
+// Targets: a point that is not finite takes no part (it is never a neighbour).
+// Queries: a query that is not finite, or lies outside the targets' box by more than max_dist, is answered "none" here.
+//   The box early-out, from monotonicity alone: every finite target b has lo <= b <= hi in each coordinate.  For a.x < lo.x,
+//   rounding is monotonic, so fl(b.x - a.x) >= fl(lo.x - a.x) = ex >= 0: the contract's |dx| is at least ex, the same on the
+//   other side with hi, and ex = 0 inside.  Squaring a non-negative float and adding non-negative floats are monotonic too:
+//   the contract's d2 of EVERY target is >= E2 = (ex*ex + ey*ey) + ez*ez, computed in the contract's order.  E2 > r2
+//   therefore means no candidate.  No margin is needed and none is taken.
+template <bool kQuery>
+__global__ __launch_bounds__(kBlock) void count_kernel(const float *__restrict__ pts, uint32_t n, Grid g, int32_t *__restrict__ cellid,
+                                                       uint32_t *__restrict__ counts, float *__restrict__ out_d2,
+                                                       int32_t *__restrict__ out_idx, uint32_t *__restrict__ stats)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    bool early = false, sorted = false;
+    if (i < n) {
+        const float *p = pts + 3 * (size_t)i;
+        const float x = p[0], y = p[1], z = p[2];
+        int c = -1;
+        if (finite3(x, y, z)) {
+            if (kQuery) {
+                const float ex = fmaxf(fmaxf(g.lo[0] - x, x - g.hi[0]), 0.f);
+                const float ey = fmaxf(fmaxf(g.lo[1] - y, y - g.hi[1]), 0.f);
+                const float ez = fmaxf(fmaxf(g.lo[2] - z, z - g.hi[2]), 0.f);
+                early = (ex * ex + ey * ey) + ez * ez > g.r2;
+            }
+            if (!early) {
+                c = (cell_of(z, g.lo[2], g.inv_h, g.g[2]) * g.g[1] + cell_of(y, g.lo[1], g.inv_h, g.g[1])) * g.g[0] +
+                    cell_of(x, g.lo[0], g.inv_h, g.g[0]);
+                atomicAdd(&counts[c], 1u);
+                sorted = true;
+            }
+        }
+        cellid[i] = c;
+        if (kQuery && c < 0) {
+            out_d2[i] = INFINITY;
+            out_idx[i] = -1;
+        }
+    }
+    // the counters: one atomic per wavefront (integer sums: the totals do not depend on the order)
+    const uint64_t be = __ballot(early), bs = __ballot(sorted);
+    if ((threadIdx.x & 63) == 0) {
+        if (kQuery && be) atomicAdd(&stats[kEarly], (uint32_t)__popcll(be));
+        if (!kQuery && bs) atomicAdd(&stats[kTargets], (uint32_t)__popcll(bs));
+    }
+}
+
+// Exclusive scan of n cell counts, in place (one workgroup; kItems consecutive cells per thread, chunks of kScan * kItems
+// cells with a carry from chunk to chunk, as fuse::scan_kernel carries one); *total = their sum when asked for.
+__global__ __launch_bounds__(kScan) void scan_kernel(uint32_t *__restrict__ cells, uint32_t n, uint32_t *__restrict__ total)
+{
+    __shared__ uint32_t s[kScan];
+    const uint32_t t = threadIdx.x;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += kScan * kItems) {  // (n <= 2^24)
+        const uint32_t k0 = base + t * kItems;
+        uint32_t v[kItems], sum = 0;
+#pragma unroll
+        for (int e = 0; e < kItems; ++e) {
+            v[e] = k0 + e < n ? cells[k0 + e] : 0u;
+            sum += v[e];
+        }
+        s[t] = sum;
+        __syncthreads();
+        for (uint32_t off = 1; off < kScan; off <<= 1) {
+            const uint32_t a = t >= off ? s[t - off] : 0u;
+            __syncthreads();
+            s[t] += a;
+            __syncthreads();
+        }
+        uint32_t run = carry + s[t] - sum;
+#pragma unroll
+        for (int e = 0; e < kItems; ++e) {
+            if (k0 + e < n) cells[k0 + e] = run;
+            run += v[e];
+        }
+        carry += s[kScan - 1];
+        __syncthreads();  // (every lane has read s[kScan - 1] before the next chunk overwrites it)
+    }
+    if (t == 0 && total) *total = carry;
+}
+
+// The scatter: cursor[] comes in as the cells' starts and goes out as their ENDS (each point takes the next free place of
+// its cell), so cell c ends up holding sorted[c ? cursor[c - 1] : 0 .. cursor[c]).
+__global__ __launch_bounds__(kBlock) void scatter_kernel(const float *__restrict__ pts, uint32_t n, const int32_t *__restrict__ cellid,
+                                                         uint32_t *__restrict__ cursor, Rec *__restrict__ sorted)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int c = cellid[i];
+    if (c < 0) return;
+    const float *p = pts + 3 * (size_t)i;
+    const uint32_t pos = atomicAdd(&cursor[c], 1u);
+    sorted[pos] = Rec{p[0], p[1], p[2], (int32_t)i};
+}
+
+// every query "none": the targets hold no finite point
+__global__ __launch_bounds__(kBlock) void none_kernel(uint32_t n, float *__restrict__ out_d2, int32_t *__restrict__ out_idx)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    out_d2[i] = INFINITY;
+    out_idx[i] = -1;
+}
+
+// The slack of the shell stop.  After shells 0 .. s every cell within Chebyshev distance s of the query's cell has been
+// visited (the grid's border clips the shells, it hides no cell).  An unvisited target b differs from the query a by at
+// least s + 1 cells along some axis k; take cell(b) >= cell(a) + s + 1, the other side is the mirror image.  With
+// t(p) = fl(fl(p - lo) * inv_h), the value cell_of floors and clamps:
+//   * t(a) < cell(a) + 1.  By definition where a's cell is not clamped; a cell clamped from below has t(a) < 0 and
+//     cell(a) = 0; a cell clamped from above is the axis' last one, and no cell lies beyond it.
+//   * t(b) >= cell(b) >= cell(a) + s + 1: b's cell is not clamped from below (it is >= 1), and a clamp from above only
+//     lowers the cell.
+//   so t(b) - t(a) > s, whatever the rounding did.  Both bounds are at most kMaxGrid + 1 = 257, and t(p) carries two
+//   roundings of relative size 2^-24 (p - lo, the product): against the real (p - lo) * inv_h each bound moves by at
+//   most 257 * 2^-23 < 2^-14 cells, so the real (b_k - a_k) * inv_h > s - 2^-13.  inv_h = fl(1 / h) >= (1 - 2^-24) / h:
+//   b_k - a_k > 0.9998 s h for s >= 1.
+//   * The contract's d2 is a sum of non-negative terms, each of dx, dx*dx and the two sums rounded once:
+//     d2 >= (b_k - a_k)^2 (1 - 2^-24)^5 > 0.9995 (s h)^2.  (No underflow: the grid is only used for 2^-40 <= h <= 2^40.)
+//   * The threshold fl(fl(fl(0.99f * s) * h)^2) <= 0.99000002^2 (1 + 2^-24)^3 (s h)^2 < 0.9802 (s h)^2.
+// Hence every unvisited target has d2 > threshold, STRICTLY, with 2 % to spare where 0.05 % are needed: it can neither
+// beat nor tie a best_d2 <= threshold, and with threshold >= r2 it is no candidate.  The stop is tested from s = 1 on.
+constexpr float kShellSlack = 0.99f;
+
+__device__ __forceinline__ void visit(const Rec *__restrict__ sorted, uint32_t beg, uint32_t end, float ax, float ay, float az, float r2,
+                                      float &best, int32_t &bj)
+{
+    for (uint32_t p = beg; p < end; ++p) {
+        const Rec b = sorted[p];
+        const float dx = ax - b.x, dy = ay - b.y, dz = az - b.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        // (bj = -1 compares as the largest index)
+        if (d2 <= r2 && (d2 < best || (d2 == best && (uint32_t)b.j < (uint32_t)bj))) {
+            best = d2;
+            bj = b.j;
+        }
+    }
+}
+
+// One lane per sorted query.  Cells are numbered x fastest, so the cells x0 .. x1 of one (y, z) row hold one contiguous
+// range of the sorted targets: a row on a y or z face of the shell is visited as one range, any other row through the
+// shell's two x ends only.
+__global__ __launch_bounds__(kBlock) void search_kernel(const Rec *__restrict__ queries, const uint32_t *__restrict__ n_sorted,
+                                                        const Rec *__restrict__ targets, const uint32_t *__restrict__ ends, Grid g,
+                                                        float *__restrict__ out_d2, int32_t *__restrict__ out_idx,
+                                                        uint32_t *__restrict__ stats)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    bool found = false;
+    if (t < *n_sorted) {
+        const Rec a = queries[t];
+        const int cx = cell_of(a.x, g.lo[0], g.inv_h, g.g[0]), cy = cell_of(a.y, g.lo[1], g.inv_h, g.g[1]),
+                  cz = cell_of(a.z, g.lo[2], g.inv_h, g.g[2]);
+        float best = INFINITY;
+        int32_t bj = -1;
+        for (int s = 0;; ++s) {
+            const int x0 = max(cx - s, 0), x1 = min(cx + s, g.g[0] - 1);
+            const int y0 = max(cy - s, 0), y1 = min(cy + s, g.g[1] - 1);
+            const int z0 = max(cz - s, 0), z1 = min(cz + s, g.g[2] - 1);
+            for (int z = z0; z <= z1; ++z)
+                for (int y = y0; y <= y1; ++y) {
+                    const int row = (z * g.g[1] + y) * g.g[0];
+                    if (abs(z - cz) == s || abs(y - cy) == s) {
+                        const int c0 = row + x0, c1 = row + x1;
+                        visit(targets, c0 ? ends[c0 - 1] : 0u, ends[c1], a.x, a.y, a.z, g.r2, best, bj);
+                    } else {  // (s >= 1 here: the two ends are different cells)
+                        if (cx - s >= 0) {
+                            const int c = row + cx - s;
+                            visit(targets, c ? ends[c - 1] : 0u, ends[c], a.x, a.y, a.z, g.r2, best, bj);
+                        }
+                        if (cx + s <= g.g[0] - 1) {
+                            const int c = row + cx + s;
+                            visit(targets, ends[c - 1], ends[c], a.x, a.y, a.z, g.r2, best, bj);
+                        }
+                    }
+                }
+            // the whole grid has been visited: the shell has left it on all six sides
+            if (cx - s <= 0 && cx + s >= g.g[0] - 1 && cy - s <= 0 && cy + s >= g.g[1] - 1 && cz - s <= 0 && cz + s >= g.g[2] - 1)
+                break;
+            if (s >= 1) {  // (see kShellSlack)
+                const float reach = (kShellSlack * (float)s) * g.h;
+                const float thr = reach * reach;
+                if ((bj >= 0 && best <= thr) || thr >= g.r2) break;
+            }
+        }
+        found = bj >= 0;
+        out_d2[a.j] = best;
+        out_idx[a.j] = bj;
+    }
+    const uint64_t b = __ballot(found);
+    if ((threadIdx.x & 63) == 0 && b) atomicAdd(&stats[kFound], (uint32_t)__popcll(b));
+}
+
+// The automatic G from n_b.  Fused clouds are surface samples: of the G^3 cells of a grid, in the order of G^2 hold
+// points.  G = ceil(sqrt(n_b / 2)) gives about two targets per occupied cell -- a first shell of some tens of distance
+// tests -- until the cap of 256 (n_b > 131072); beyond it the cells fill up in proportion to n_b.
+inline int automatic_grid(int64_t n_targets)
+{
+    const int g = (int)ceil(sqrt((double)n_targets / 2.0));
+    return g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g;
+}
+
+}  // namespace cloud
+
+namespace {
+
+thread_local int64_t last_stats[6] = {0, 0, 0, 0, 0, 0};  // gipuma_hip_cloud_last_stats
+
+// the call's scratch: freed on every way out of gipuma_hip_cloud_nearest
+struct Scratch {
+    float *partial = nullptr, *box = nullptr;
+    uint32_t *cells_b = nullptr, *cells_a = nullptr, *stats = nullptr;
+    int32_t *cellid_b = nullptr, *cellid_a = nullptr;
+    cloud::Rec *sorted_b = nullptr, *sorted_a = nullptr;
+    hipStream_t st = nullptr, own = nullptr;
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~Scratch()
+    {
+        if (st) (void)hipStreamSynchronize(st);  // (nothing of this call is in flight when its buffers go)
+        (void)hipFree(partial);
+        (void)hipFree(box);
+        (void)hipFree(cells_b);
+        (void)hipFree(cells_a);
+        (void)hipFree(stats);
+        (void)hipFree(cellid_b);
+        (void)hipFree(cellid_a);
+        (void)hipFree(sorted_b);
+        (void)hipFree(sorted_a);
+        for (hipEvent_t ev : e)
+            if (ev) (void)hipEventDestroy(ev);
+        if (own) (void)hipStreamDestroy(own);
+    }
+};
+
+inline dim3 blocks_for(uint32_t n) { return dim3((n + cloud::kBlock - 1) / cloud::kBlock); }
+
+int run(const gipuma_hip_cloud_desc *d, float *d2_dev, int32_t *idx_dev, int64_t counts[2], float *device_ms)
+{
+    using namespace cloud;
+    const uint32_t na = (uint32_t)d->n_queries, nb = (uint32_t)d->n_targets;
+    HIP_OK(hipSetDevice(d->device_id));
+    Scratch sc;
+    if (d->stream) {
+        sc.st = (hipStream_t)d->stream;
+    } else {
+        HIP_OK(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
+        sc.st = sc.own;
+    }
+    hipStream_t st = sc.st;
+    for (hipEvent_t &ev : sc.e) HIP_OK(hipEventCreate(&ev));
+    const dim3 block(kBlock);
+    float ms_box = 0.f, ms_rest = 0.f;
+    int64_t found = 0;
+
+    // the box of the finite targets
+    float box[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    if (na && nb) {
+        const int nblocks = (int)(blocks_for(nb).x < (uint32_t)kBoxBlocks ? blocks_for(nb).x : (uint32_t)kBoxBlocks);
+        HIP_OK(hipMalloc(&sc.partial, sizeof(float) * 6 * nblocks));
+        HIP_OK(hipMalloc(&sc.box, sizeof box));
+        HIP_OK(hipEventRecord(sc.e[0], st));
+        hipLaunchKernelGGL(box_partial_kernel, dim3(nblocks), block, 0, st, d->targets, nb, sc.partial);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(box_final_kernel, dim3(1), block, 0, st, sc.partial, nblocks, sc.box);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(sc.e[1], st));
+        HIP_OK(hipMemcpyAsync(box, sc.box, sizeof box, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(&ms_box, sc.e[0], sc.e[1]));
+    }
+    const bool any_target = box[0] <= box[3] && box[1] <= box[4] && box[2] <= box[5];
+
+    if (na && !any_target) {
+        HIP_OK(hipEventRecord(sc.e[2], st));
+        hipLaunchKernelGGL(none_kernel, blocks_for(na), block, 0, st, na, d2_dev, idx_dev);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(sc.e[3], st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(&ms_rest, sc.e[2], sc.e[3]));
+    } else if (na) {
+        // the grid: one cell edge h for all axes, G cells along the longest one; an axis of zero extent gets one cell
+        Grid g;
+        float ext[3], longest = 0.f;
+        for (int k = 0; k < 3; ++k) {
+            g.lo[k] = box[k];
+            g.hi[k] = box[3 + k];
+            ext[k] = box[3 + k] - box[k];
+            longest = fmaxf(longest, ext[k]);
+        }
+        g.r2 = d->max_dist * d->max_dist;
+        int G = d->grid ? d->grid : automatic_grid(d->n_targets);
+        g.h = longest / (float)G;
+        // one cell -- the brute force -- where the derivation of kShellSlack does not hold: h outside 2^-40 .. 2^40 (squares
+        // would underflow or overflow), an infinite extent or an infinite r2
+        if (!(g.h >= 0x1p-40f && g.h <= 0x1p40f) || !std::isfinite(g.r2)) G = 1;
+        if (G == 1) g.h = 1.f;
+        g.inv_h = 1.f / g.h;
+        for (int k = 0; k < 3; ++k) {
+            const int cells = G == 1 || !(ext[k] > 0.f) ? 1 : (int)floorf(ext[k] * g.inv_h) + 1;
+            g.g[k] = cells < 1 ? 1 : cells > G ? G : cells;
+        }
+        const uint32_t ncells = (uint32_t)g.g[0] * g.g[1] * g.g[2];
+        last_stats[0] = G;
+        for (int k = 0; k < 3; ++k) last_stats[1 + k] = g.g[k];
+
+        HIP_OK(hipMalloc(&sc.cells_b, sizeof(uint32_t) * ncells));
+        HIP_OK(hipMalloc(&sc.cells_a, sizeof(uint32_t) * ncells));
+        HIP_OK(hipMalloc(&sc.stats, sizeof(uint32_t) * kStats));
+        HIP_OK(hipMalloc(&sc.cellid_b, sizeof(int32_t) * nb));
+        HIP_OK(hipMalloc(&sc.cellid_a, sizeof(int32_t) * na));
+        HIP_OK(hipMalloc(&sc.sorted_b, sizeof(Rec) * nb));
+        HIP_OK(hipMalloc(&sc.sorted_a, sizeof(Rec) * na));
+
+        HIP_OK(hipEventRecord(sc.e[2], st));
+        HIP_OK(hipMemsetAsync(sc.cells_b, 0, sizeof(uint32_t) * ncells, st));
+        HIP_OK(hipMemsetAsync(sc.cells_a, 0, sizeof(uint32_t) * ncells, st));
+        HIP_OK(hipMemsetAsync(sc.stats, 0, sizeof(uint32_t) * kStats, st));
+        hipLaunchKernelGGL(count_kernel<false>, blocks_for(nb), block, 0, st, d->targets, nb, g, sc.cellid_b, sc.cells_b,
+                           (float *)nullptr, (int32_t *)nullptr, sc.stats);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScan), 0, st, sc.cells_b, ncells, (uint32_t *)nullptr);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(scatter_kernel, blocks_for(nb), block, 0, st, d->targets, nb, sc.cellid_b, sc.cells_b, sc.sorted_b);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(count_kernel<true>, blocks_for(na), block, 0, st, d->queries, na, g, sc.cellid_a, sc.cells_a, d2_dev,
+                           idx_dev, sc.stats);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScan), 0, st, sc.cells_a, ncells, sc.stats + kSearched);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(scatter_kernel, blocks_for(na), block, 0, st, d->queries, na, sc.cellid_a, sc.cells_a, sc.sorted_a);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(search_kernel, blocks_for(na), block, 0, st, sc.sorted_a, sc.stats + kSearched, sc.sorted_b, sc.cells_b, g,
+                           d2_dev, idx_dev, sc.stats);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(sc.e[3], st));
+        uint32_t stats[kStats];
+        HIP_OK(hipMemcpyAsync(stats, sc.stats, sizeof stats, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(&ms_rest, sc.e[2], sc.e[3]));
+        found = stats[kFound];
+        last_stats[4] = stats[kEarly];
+        last_stats[5] = stats[kSearched];
+    }
+    if (counts) {
+        counts[0] = found;
+        counts[1] = (int64_t)na - found;
+    }
+    if (device_ms) *device_ms = ms_box + ms_rest;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gipuma_hip_cloud_nearest(const gipuma_hip_cloud_desc *d, float *d2_dev, int32_t *idx_dev, int64_t counts[2], float *device_ms)
+{
+    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
+    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "cloud: abi_version mismatch");
+    if (d->n_queries < 0 || d->n_targets < 0) return fail(GIPUMA_HIP_ERR_ARG, "cloud: negative point count");
+    if (d->n_queries >= (1ll << 31) || d->n_targets >= (1ll << 31))
+        return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "cloud: a cloud may hold at most 2^31 - 1 points");
+    if ((d->n_queries && (!d->queries || !d2_dev || !idx_dev)) || (d->n_targets && !d->targets))
+        return fail(GIPUMA_HIP_ERR_ARG, "cloud: null pointer with a non-zero point count");
+    if (!(d->max_dist > 0.f) || !std::isfinite(d->max_dist)) return fail(GIPUMA_HIP_ERR_ARG, "cloud: max_dist must be > 0 and finite");
+    if (d->grid < 0 || d->grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "cloud: grid must be 0 (automatic) or 1..256");
+    if (const int rc = pm_host::check_device(d->device_id)) return rc;
+    memset(last_stats, 0, sizeof last_stats);
+    return run(d, d2_dev, idx_dev, counts, device_ms);
+}
+
+int gipuma_hip_cloud_last_stats(int64_t stats[6])
+{
+    if (!stats) return fail(GIPUMA_HIP_ERR_ARG, "null argument");
+    memcpy(stats, last_stats, sizeof last_stats);
+    return 0;
+}
+
+}  // extern "C"

@@ -2,6 +2,8 @@
 h*w*nb float32, row-major.  `disp.dmb` holds norm4.w (depth), `normals.dmb` the world normals
 (main.cpp:1001-1015); these are the "CPU-readable dumps" the depth-map fusion reads (gipuma_amd.fusion, the in-tree
 consumer in place of the external fusibile tool of the reference's scripts)."""
+import os
+
 import numpy as np
 
 
@@ -91,3 +93,114 @@ def read_ply_binary(path):
             if line.strip() == b"end_header":
                 break
         return np.fromfile(f, dtype=_PLY_VERTEX, count=n)
+
+
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+                "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+                "double": "f8", "float64": "f8"}
+
+
+def _ply_header(f, path):
+    """-> (format, [(element name, count, [(property name, scalar type or ("list", count type, item type))])])"""
+    if f.readline().strip() != b"ply":
+        raise ValueError("%s: not a PLY file" % path)
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError("%s: no end_header" % path)
+        w = line.decode("ascii", "replace").split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "end_header":
+            break
+        try:
+            if w[0] == "format":
+                fmt = w[1]
+            elif w[0] == "element":
+                elements.append((w[1], int(w[2]), []))
+            elif w[0] == "property" and elements and w[1] == "list":
+                elements[-1][2].append((w[4], ("list", _PLY_SCALARS[w[2]], _PLY_SCALARS[w[3]])))
+            elif w[0] == "property" and elements:
+                elements[-1][2].append((w[2], _PLY_SCALARS[w[1]]))
+            else:
+                raise ValueError
+        except (IndexError, KeyError, ValueError):
+            raise ValueError("%s: header line not understood: %r" % (path, line))
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError("%s: format %s is not read here (binary_little_endian and ascii are)" % (path, fmt))
+    if any(n < 0 for _, n, _ in elements):
+        raise ValueError("%s: negative element count" % path)
+    return fmt, elements
+
+
+def _ply_skip_binary(f, path, count, props):
+    """moves past `count` binary elements, each property by its declared size"""
+    if all(not isinstance(t, tuple) for _, t in props):
+        f.seek(count * sum(np.dtype(t).itemsize for _, t in props), 1)
+        return
+    for _ in range(count):  # (lists: every element has its own size)
+        for _, t in props:
+            if isinstance(t, tuple):
+                raw = f.read(np.dtype(t[1]).itemsize)
+                if len(raw) < np.dtype(t[1]).itemsize:
+                    raise ValueError("%s: file ends inside an element" % path)
+                f.seek(int(np.frombuffer(raw, dtype="<" + t[1])[0]) * np.dtype(t[2]).itemsize, 1)
+            else:
+                f.seek(np.dtype(t).itemsize, 1)
+
+
+def read_ply_xyz(path):
+    """The x, y, z of a PLY file's element `vertex` as an (n, 3) float32 array, in file order.  Driven by the header:
+    binary_little_endian or ascii, x / y / z declared float or double, every other property and every other element
+    skipped by its declared size -- reference scans do not come in this project's own vertex layout, which is all
+    read_ply_binary reads.  ValueError for a malformed or truncated file, a vertex without x, y or z, binary_big_endian
+    and a vertex count the file cannot hold -- raised before anything of the claimed size is allocated."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        names = [e[0] for e in elements]
+        if "vertex" not in names:
+            raise ValueError("%s: no element vertex" % path)
+        k = names.index("vertex")
+        _, n, props = elements[k]
+        pnames = [p for p, _ in props]
+        for c in ("x", "y", "z"):
+            if c not in pnames:
+                raise ValueError("%s: element vertex has no property %s" % (path, c))
+            if props[pnames.index(c)][1] not in ("f4", "f8"):
+                raise ValueError("%s: property %s must be float or double" % (path, c))
+        if fmt == "binary_little_endian":
+            for _, cnt, pr in elements[:k]:
+                _ply_skip_binary(f, path, cnt, pr)
+            if any(isinstance(t, tuple) for _, t in props):
+                raise ValueError("%s: a list property in element vertex is not read here" % path)
+            dt = np.dtype([(("p%d" % i) if p not in ("x", "y", "z") else p, "<" + t) for i, (p, t) in enumerate(props)])
+            if f.tell() > size or n * dt.itemsize > size - f.tell():
+                raise ValueError("%s: the file cannot hold %d vertices of %d bytes" % (path, n, dt.itemsize))
+            v = np.fromfile(f, dtype=dt, count=n)
+            return np.stack([v["x"], v["y"], v["z"]], axis=-1).astype(np.float32).reshape(n, 3)
+        # ascii: one element per line, a vertex of three one-digit numbers takes 6 bytes
+        for _, cnt, _ in elements[:k]:
+            for _ in range(cnt):
+                if not f.readline():
+                    raise ValueError("%s: file ends before element vertex" % path)
+        if n * 6 > size - f.tell() + 1:
+            raise ValueError("%s: the file cannot hold %d vertices" % (path, n))
+        out = np.empty((n, 3), dtype=np.float32)
+        for r in range(n):
+            w = f.readline().split()
+            at, col = 0, {}
+            try:
+                for p, t in props:
+                    if isinstance(t, tuple):
+                        at += 1 + int(w[at])
+                    else:
+                        col[p] = w[at]
+                        at += 1
+                if at > len(w):
+                    raise IndexError
+                out[r] = [float(col["x"]), float(col["y"]), float(col["z"])]
+            except (IndexError, ValueError):
+                raise ValueError("%s: vertex %d of %d is incomplete" % (path, r, n))
+        return out

@@ -369,6 +369,39 @@ typedef struct gipuma_hip_prior_desc {
  * one stream, or let the first finish. */
 int gipuma_hip_prior_from_views(const gipuma_hip_prior_desc *desc, float *prior_dev, int64_t counts[3], float *device_ms);
 
+/* ---- nearest neighbours between two point clouds: the search behind the cloud score ----
+ * For every query a_i (n_queries packed float32 xyz) the nearest target b_j (n_targets packed xyz) within max_dist.
+ * Float32 without contraction, r2 = max_dist * max_dist:
+ *     dx = a_i.x - b_j.x;  dy = a_i.y - b_j.y;  dz = a_i.z - b_j.z;  d2 = (dx*dx + dy*dy) + dz*dz
+ *     j is a candidate  iff  b_j is finite in all three coordinates  and  d2 <= r2   (the radius is inclusive)
+ *     d2_dev[i]  = the minimum of d2 over the candidates;  idx_dev[i] = the lowest j that attains it
+ *     no candidate, or a_i not finite:  d2_dev[i] = +inf,  idx_dev[i] = -1
+ * A minimum and a lowest index do not depend on the order of the candidates: the result is defined without reference
+ * to the uniform grid the kernels search with, and it equals a brute-force search in every bit (tests/cloud_ref.py).
+ * The grid -- one cell edge on all axes, `grid` cells along the longest axis of the finite targets' bounding box --
+ * changes the time only; 0 lets the library choose it from n_targets, ceil(sqrt(n_targets / 2)) capped at 256.
+ * n_queries = 0 writes nothing; n_targets = 0 answers "none" everywhere.  Blocks until the result is complete; the
+ * clouds must be complete on desc->stream's terms when the call is made.  Scratch (about 20 bytes per point and 8 per
+ * cell) is allocated for the call and freed before it returns, on every error path too. */
+typedef struct gipuma_hip_cloud_desc {
+    uint32_t abi_version;           /* GIPUMA_HIP_ABI_VERSION */
+    int64_t n_queries, n_targets;   /* each < 2^31; more: GIPUMA_HIP_ERR_UNSUPPORTED */
+    const float *queries, *targets; /* device pointers, packed xyz float32 */
+    float max_dist;                 /* > 0 and finite, else GIPUMA_HIP_ERR_ARG */
+    int32_t grid;                   /* 0: automatic; 1..256: cells along the longest axis */
+    int32_t device_id;              /* HIP device ordinal */
+    void *stream;                   /* hipStream_t to launch on, NULL = one the library creates for the call */
+} gipuma_hip_cloud_desc;
+
+/* d2_dev, idx_dev: n_queries entries each, device.  counts (queries that found a neighbour, queries that did not) and
+ * device_ms (HIP events around the launches) may be NULL. */
+int gipuma_hip_cloud_nearest(const gipuma_hip_cloud_desc *desc, float *d2_dev, int32_t *idx_dev, int64_t counts[2],
+                             float *device_ms);
+/* What the calling thread's last gipuma_hip_cloud_nearest did: the cells along the longest axis, the cells along x, y
+ * and z, the queries answered "none" without a search (farther than max_dist from the targets' bounding box) and the
+ * queries searched.  All 0 after a call that had no finite target or no query. */
+int gipuma_hip_cloud_last_stats(int64_t stats[6]);
+
 #ifdef __cplusplus
 }
 #endif
