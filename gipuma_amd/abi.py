@@ -131,6 +131,15 @@ class CloudDesc(C.Structure):
     ]
 
 
+class ThinDesc(C.Structure):
+    """gipuma_hip_thin_desc: one device cloud of packed float32 xyz, the minimum spacing, the order's seed and kind (0
+    hashed, 1 index) and the grid (0: automatic)"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("n_points", C.c_int64), ("points", C.c_void_p), ("radius", C.c_float),
+        ("seed", C.c_uint32), ("order", C.c_int32), ("grid", C.c_int32), ("device_id", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
 # every symbol include/gipuma_hip.h declares: (name, restype, argtypes)
 _FP = C.POINTER(C.c_float)
 SYMBOLS = [
@@ -166,6 +175,7 @@ SYMBOLS = [
     ("gipuma_hip_prior_from_views", C.c_int, [C.POINTER(PriorDesc), C.c_void_p, C.POINTER(C.c_int64), _FP]),
     ("gipuma_hip_cloud_nearest", C.c_int, [C.POINTER(CloudDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), _FP]),
     ("gipuma_hip_cloud_last_stats", C.c_int, [C.POINTER(C.c_int64)]),
+    ("gipuma_hip_cloud_thin", C.c_int, [C.POINTER(ThinDesc), C.c_void_p, C.POINTER(C.c_int64), _FP]),
 ]
 
 _lib = None

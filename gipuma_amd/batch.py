@@ -33,7 +33,8 @@ MI355X-first differences from the shell loop:
     WORLD_SIZE > 1 run `python -m gipuma_amd.fusion` on the output folder instead;
   * --eval_cloud gt.ply (with --fuse): the fused cloud is scored against that reference cloud on the GPU -- accuracy,
     completeness, precision / recall / F-score within --eval_max_dist (gipuma_amd.cloud_eval) -- and the
-    score joins the report as `cloud_score`.
+    score joins the report as `cloud_score`.  --eval_reduce 0.2 thins the fused cloud to that minimum point spacing
+    first, as DTU's evaluation does.
 
 Images: what the reference's scripts hand to imread (main.cpp:739-751) -- PNG, JPG (through PIL), binary PGM / PPM.
 Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
@@ -319,15 +320,22 @@ def parse_args(argv):
                     help="with --fuse: a reference cloud (PLY) to score the fused cloud against (gipuma_amd.cloud_eval)")
     pa.add_argument("--eval_max_dist", type=float, default=20.0,
                     help="with --eval_cloud: distances beyond it are discarded")
+    pa.add_argument("--eval_reduce", type=float, default=0.0,
+                    help="with --eval_cloud: thin the fused cloud to this minimum point spacing before it is scored "
+                         "(0: off; DTU uses 0.2; DESIGN.md 15)")
     args = pa.parse_args(argv)
     # the reference parses these with sscanf("%f") into float fields (main.cpp:300-360)
     for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
-              "normal_thresh", "eval_max_dist"):
+              "normal_thresh", "eval_max_dist", "eval_reduce"):
         setattr(args, k, float(np.float32(getattr(args, k))))
     if args.eval_cloud is not None and not args.fuse:
         pa.error("--eval_cloud scores the fused cloud: it needs --fuse")
     if args.eval_cloud is not None and not (args.eval_max_dist > 0 and np.isfinite(args.eval_max_dist)):
         pa.error("--eval_max_dist must be > 0 and finite")
+    if not (args.eval_reduce >= 0 and np.isfinite(args.eval_reduce)):
+        pa.error("--eval_reduce must be >= 0 and finite (0: off)")
+    if args.eval_reduce > 0 and args.eval_cloud is None:
+        pa.error("--eval_reduce thins the cloud that --eval_cloud scores: it needs --eval_cloud")
     if args.levels < 1:
         raise SystemExit("--levels must be >= 1")
     args.level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
@@ -373,7 +381,7 @@ def score_fused(scan):
     from . import cloud_eval
     args = scan.args
     out = cloud_eval.score(scan.fused_xyz, dmb.read_ply_xyz(args.eval_cloud), args.eval_max_dist,
-                           device_id=scan.dev[0].device.index)
+                           device_id=scan.dev[0].device.index, reduce=args.eval_reduce)
     out["reference"] = args.eval_cloud
     return out
 

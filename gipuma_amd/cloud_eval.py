@@ -1,14 +1,18 @@
-"""Score a point cloud against a reference cloud on the GPU: accuracy and completeness.
+"""Score a point cloud against a reference cloud on the GPU: accuracy and completeness, after thinning
+the cloud to a minimum point spacing when asked to.
 
     python -m gipuma_amd.cloud_eval --cloud fused.ply --reference gt.ply --max_dist 20 --thresholds 0.5,1,2 \\
-        [--output report.json]
+        [--reduce 0.2 [--reduce_reference] [--seed N]] [--output report.json]
 
 DTU -- the data set this project is calibrated on -- scores a reconstruction cloud against cloud: accuracy is the distance
 from each reconstructed point to the nearest reference point, completeness the same the other way round, distances beyond
 a cut-off discarded.  Both directions are one nearest-neighbour search each (gipuma_hip_cloud_nearest,
 gipuma_amd/csrc/gipuma_cloud.hip: gfx950 kernels over a uniform grid, equal to a brute-force search in every bit).  There
-is no CPU fallback.  Not part of the score here: DTU's density normalisation of the clouds (its 0.2 mm resampling),
-observability masks and ground-plane removal.
+is no CPU fallback.  The means of the score are means over points, so they are weighted by how densely the fusion happened
+to sample each surface; DTU removes that by thinning the reconstruction to a minimum spacing first (its 0.2 mm resampling).
+--reduce does the same here (gipuma_hip_cloud_thin: points visited in a hashed order, a point kept unless a kept point lies
+within the spacing), and `thin` offers it for the delivered cloud.  Not part of the score here: DTU's observability masks
+and ground-plane removal.
 """
 import argparse
 import ctypes as C
@@ -21,6 +25,8 @@ from . import abi, dmb
 
 THRESHOLDS = (0.5, 1.0, 2.0)
 _STATS = ("grid", "cells_x", "cells_y", "cells_z", "early_out", "searched")
+ORDERS = {"hashed": 0, "index": 1}
+_THIN_INFO = ("kept", "dropped", "not_finite", "rounds", "grid", "cells_x", "cells_y", "cells_z")
 
 
 def _device_cloud(a, device, keep):
@@ -63,6 +69,40 @@ def nearest(queries, targets, max_dist, grid=0, device_id=0, return_info=False):
     return out + (dict(found=int(counts[0]), none=int(counts[1]), **{k: int(v) for k, v in zip(_STATS, stats)}),)
 
 
+def thin_mask(points, radius, seed=0, order="hashed", grid=0, device_id=0):
+    """The contract of gipuma_hip_cloud_thin on the (n, 3) cloud `points` (a numpy array or a torch tensor; a device
+    tensor is passed by pointer): (keep, device_ms, info) -- keep a torch uint8 tensor on the device, one byte per point,
+    info dict(kept, dropped, not_finite, rounds, grid, cells_x, cells_y, cells_z)."""
+    import torch
+    if order not in ORDERS:
+        raise ValueError("order is 'hashed' or 'index', got %r" % (order,))
+    lib = abi.load_library()
+    if lib.gipuma_hip_device_count() < 1:
+        raise abi.GipumaHipError("thinning a cloud needs a HIP device; gipuma_amd has no CPU fallback")
+    dev, held = torch.device("cuda", device_id), []
+    d = abi.ThinDesc()
+    d.abi_version = abi.ABI_VERSION
+    d.points, d.n_points = _device_cloud(points, dev, held)
+    d.radius, d.seed, d.order, d.grid, d.device_id = float(radius), int(seed) & 0xFFFFFFFF, ORDERS[order], int(grid), device_id
+    keep = torch.empty(d.n_points, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)  # (the library works on a stream of its own: the cloud must be complete)
+    info, ms = (C.c_int64 * len(_THIN_INFO))(), C.c_float()
+    abi.check(lib, lib.gipuma_hip_cloud_thin(C.byref(d), keep.data_ptr() if d.n_points else None, info, C.byref(ms)),
+              "gipuma_hip_cloud_thin")
+    return keep, ms.value, {k: int(v) for k, v in zip(_THIN_INFO, info)}
+
+
+def thin(points, radius, seed=0, order="hashed", grid=0, device_id=0, return_info=False):
+    """Thins a cloud to a minimum point spacing: the points are visited in ascending (prio(i), i) -- a hash
+    of seed and index, or with order="index" the caller's own order -- and a point is kept unless a point kept before it
+    lies within `radius` (inclusive).  Returns the ascending int64 indices of the kept points (numpy); with return_info
+    also device_ms and dict(kept, dropped, not_finite, rounds, grid, cells_x, cells_y, cells_z)."""
+    import torch
+    keep, ms, info = thin_mask(points, radius, seed, order, grid, device_id)
+    idx = torch.nonzero(keep).reshape(-1).cpu().numpy().astype(np.int64)
+    return (idx, ms, info) if return_info else idx
+
+
 def direction_score(d2, thresholds):
     """One direction of the score from its squared distances (float32, +inf: none): ({mean, median, found, none} over the
     points that found a neighbour, [share of ALL points with d <= tau for tau in thresholds] -- "none" is a miss)."""
@@ -81,18 +121,43 @@ def combine(acc, prec, comp, rec, thresholds):
     return out
 
 
-def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device_id=0):
+def _reduced(a, radius, seed, device_id):
+    """the cloud `a` thinned to `radius` (thin, hashed order), as a device tensor, and (device_ms, rounds)"""
+    import torch
+    idx, ms, info = thin(a, radius, seed=seed, device_id=device_id, return_info=True)
+    dev = torch.device("cuda", device_id)
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    return t.to(device=dev, dtype=torch.float32)[torch.from_numpy(idx).to(dev)], (ms, info["rounds"])
+
+
+def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device_id=0, reduce=0.0, reduce_reference=False,
+          seed=0):
     """Both directions of the score.  accuracy: {mean, median, found, none} of d = sqrt(d2) (float64, on the host) over
     the cloud's points that found a reference point within max_dist; completeness: the same over the reference's points;
     precision / recall per threshold: the share of ALL cloud / reference points with d <= tau; fscore = 2PR / (P + R), 0
-    when both are 0.  Empty clouds give NaN means and 0 counts.  Also the point counts, both device times and the grids."""
+    when both are 0.  Empty clouds give NaN means and 0 counts.  Also the point counts, both device times and the grids.
+    reduce > 0: the cloud is thinned to that spacing (thin, hashed order with `seed`) before both searches, with
+    reduce_reference the reference too -- DTU thins the reconstruction only.  The report then also carries reduce,
+    cloud_points_before, reference_points_before, thin_rounds and thin_device_ms (cloud first, then the reference)."""
     thresholds = [float(t) for t in thresholds]
+    if not (reduce >= 0 and np.isfinite(reduce)):
+        raise ValueError("reduce must be >= 0 and finite, got %r" % (reduce,))
+    before, thinned = (int(cloud.shape[0]), int(reference.shape[0])), []
+    if reduce > 0:
+        cloud, t = _reduced(cloud, reduce, seed, device_id)
+        thinned.append(t)
+        if reduce_reference:
+            reference, t = _reduced(reference, reduce, seed, device_id)
+            thinned.append(t)
     a_d2, _, a_ms, a_info = nearest(cloud, reference, max_dist, grid, device_id, return_info=True)
     c_d2, _, c_ms, c_info = nearest(reference, cloud, max_dist, grid, device_id, return_info=True)
     out = combine(*direction_score(a_d2, thresholds), *direction_score(c_d2, thresholds), thresholds)
     out.update({"max_dist": float(max_dist), "cloud_points": int(len(a_d2)), "reference_points": int(len(c_d2)),
                 "accuracy_device_ms": a_ms, "completeness_device_ms": c_ms,
                 "accuracy_search": {k: a_info[k] for k in _STATS}, "completeness_search": {k: c_info[k] for k in _STATS}})
+    if reduce > 0:
+        out.update({"reduce": float(reduce), "cloud_points_before": before[0], "reference_points_before": before[1],
+                    "thin_rounds": [r for _, r in thinned], "thin_device_ms": [ms for ms, _ in thinned]})
     return out
 
 
@@ -104,6 +169,10 @@ def parse_args(argv):
     pa.add_argument("--thresholds", default=",".join("%g" % t for t in THRESHOLDS),
                     help="comma separated distances of the precision / recall / F-score")
     pa.add_argument("--grid", type=int, default=0, help="cells along the longest axis (0: automatic, 1..256)")
+    pa.add_argument("--reduce", type=float, default=0.0,
+                    help="thin the cloud to this minimum point spacing before scoring (0: off; DTU uses 0.2)")
+    pa.add_argument("--reduce_reference", action="store_true", help="with --reduce: thin the reference as well")
+    pa.add_argument("--seed", type=int, default=0, help="with --reduce: seed of the order the points are visited in")
     pa.add_argument("--device", type=int, default=0)
     pa.add_argument("--output", default=None, help="write the report (JSON) here")
     args = pa.parse_args(argv)
@@ -118,13 +187,21 @@ def parse_args(argv):
         pa.error("--thresholds needs at least one distance, each >= 0 and finite")
     if not 0 <= args.grid <= 256:
         pa.error("--grid must be 0 (automatic) or 1..256")
+    args.reduce = float(np.float32(args.reduce))
+    if not (args.reduce >= 0 and np.isfinite(args.reduce)):
+        pa.error("--reduce must be >= 0 and finite (0: off)")
+    if args.reduce_reference and not args.reduce > 0:
+        pa.error("--reduce_reference needs --reduce")
+    if not 0 <= args.seed < 2 ** 32:
+        pa.error("--seed must be 0 .. 2^32 - 1")
     return args
 
 
 def main(argv=None):
     args = parse_args(argv)
     report = score(dmb.read_ply_xyz(args.cloud), dmb.read_ply_xyz(args.reference), args.max_dist, args.thresholds,
-                   grid=args.grid, device_id=args.device)
+                   grid=args.grid, device_id=args.device, reduce=args.reduce, reduce_reference=args.reduce_reference,
+                   seed=args.seed)
     report.update({"cloud": args.cloud, "reference": args.reference})
     if args.output:
         with open(args.output, "w") as f:
@@ -135,6 +212,11 @@ def main(argv=None):
              report["completeness"]["mean"], report["completeness"]["median"], report["completeness"]["found"],
              report["reference_points"], "/".join("%.4f" % f for f in report["fscore"]),
              "/".join("%g" % t for t in args.thresholds), report["accuracy_device_ms"], report["completeness_device_ms"]))
+    if args.reduce > 0:
+        print("thinned to a spacing of %g first: cloud %d -> %d points, reference %d -> %d, %s rounds, %s ms on device"
+              % (args.reduce, report["cloud_points_before"], report["cloud_points"], report["reference_points_before"],
+                 report["reference_points"], "/".join("%d" % r for r in report["thin_rounds"]),
+                 "/".join("%.2f" % m for m in report["thin_device_ms"])))
     return 0
 
 

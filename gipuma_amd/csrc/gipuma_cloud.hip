@@ -23,6 +23,9 @@
 // The histogram and the scatter use integer atomics (as the prior's z-buffer does), so the order of the points INSIDE a
 // cell varies from run to run.  The contract's result does not depend on that order: the search carries (d2, j) compared
 // lexicographically, and a cell's points are all visited or all skipped.
+//
+// The same grid has a second client: thinning a cloud to a minimum point spacing (namespace thin below, DESIGN.md 15,
+// gipuma_hip_cloud_thin), the density normalisation that comes before the score.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -315,6 +318,137 @@ inline int automatic_grid(int64_t n_targets)
 
 }  // namespace cloud
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Thinning to a minimum point spacing (restated on the CPU by tests/thin_ref.py).  The contract, defined
+// without any grid: the finite points are visited in ascending key(i) = (prio(i), i); a point is KEPT iff no point kept
+// before it has d2 <= r2 (cloud's d2, inclusive radius) -- the lexicographically first maximal independent set of the
+// radius graph.  A point that is not finite is never kept and never suppresses.
+//
+// Launches, all on one stream:
+//   cloud::box_*, count_kernel<false>, scan_kernel, scatter_kernel    the box of the finite points and their counting sort
+//                                                  by cell, once, exactly as for the search's targets
+//   thin::round_kernel, once per round t = 1, 2, ...   one lane per UNDECIDED point, taken from a worklist of sorted
+//                                                  positions; survivors are appended to the other worklist (one ballot
+//                                                  and one atomicAdd per wavefront); the host reads the 4-byte survivor
+//                                                  count and sizes the next launch
+// One uint32 of state per SORTED POSITION (a cell's states are contiguous, like its records): 0 = undecided, a point
+// decided in round t stores 2t + kept.  In round t a reader takes a state s for decided only if (s >> 1) < t: a value
+// stored in the current round reads as undecided whether or not the reader sees it, so the in-place plain stores give
+// synchronous (Jacobi) rounds and every run decides the same points in the same round.  Lane i, over the neighbours
+// j != i with d2 <= r2 and key(j) < key(i):
+//     some such j decided-kept         -> i is DROPPED (and may stop looking)
+//     else no such j undecided         -> i is KEPT
+//     else                             -> i stays undecided
+// By induction over the key both decisions are the sequential pass's: i is decided only from lower-key neighbours whose
+// decisions are final, and those are all the sequential pass looks at.  The lowest-key undecided point has no undecided
+// lower-key neighbour, so every round decides at least one point: the host stops with an error if one does not.
+// Cells are visited whole and both tests are "exists" predicates: the order of the points inside a cell cannot matter.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace thin {
+
+using cloud::cell_of;
+using cloud::Grid;
+using cloud::kBlock;
+using cloud::Rec;
+
+enum { kKept = cloud::kStats, kSurvivors, kCounters };  // the device counters, behind cloud's (kTargets: the finite points)
+
+// The reach of a lane's cell range.  Lane a visits, per axis k, the cells cell_of(fl(a_k - reach)) .. cell_of(fl(a_k +
+// reach)) with reach = fl(kReach * radius).  No neighbour is skipped: let b be finite with d2(a, b) <= r2.
+//   * d2 is a sum of non-negative floats and rounding is monotonic, so fl(d_k * d_k) <= d2 <= r2 = fl(radius * radius)
+//     <= radius^2 (1 + 2^-24) for d_k = fl(a_k - b_k).  Either d_k * d_k < 2^-126, and then |d_k| < 2^-63 < radius, or
+//     the product is rounded with relative error 2^-24: d_k^2 <= radius^2 (1 + 2^-24) / (1 - 2^-24).  A difference of
+//     floats never underflows, |a_k - b_k| <= |d_k| / (1 - 2^-24).  Together the REAL |a_k - b_k| <= radius (1 + 2^-22).
+//   * reach >= 1.01 (1 - 2^-24)^2 radius > 1.009 radius (kReach is 1.01 rounded to a float; no underflow, the grid is
+//     only used for 2^-40 <= radius <= 2^40), so the real x = a_k - reach < a_k - radius (1 + 2^-22) <= b_k.  b_k is a
+//     float and rounding is monotonic: b_k >= fl(x), the value the lane computes.  An overflow to -inf only lowers it.
+//   * cell_of is monotonic: cell_of(b_k) >= cell_of(fl(a_k - reach)).  The upper end is the mirror image.
+// Nothing here depends on how cell_of rounds, only on its monotonicity; the slack of 0.9 % is spent on a bound that
+// needs 2^-22.  Outside 2^-40 .. 2^40 (radius or cell edge) the host takes G = 1: one cell, every point visited.
+constexpr float kReach = 1.01f;
+
+// prio(i) of the hashed order: mix32(mix32(seed + 0x9E3779B9) ^ (i + 0x85EBCA6B)); salt is the inner mix32, from the host.
+// (mix32 is pm_core.h's, restated: that header would bring the solver's pack kernels into this unit.)
+__host__ __device__ __forceinline__ uint32_t mix32(uint32_t h)
+{
+    h ^= h >> 16;
+    h *= 0x7feb352dU;
+    h ^= h >> 15;
+    h *= 0x846ca68bU;
+    h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ uint32_t prio_of(int32_t i, uint32_t salt, bool hashed) { return hashed ? mix32(salt ^ ((uint32_t)i + 0x85EBCA6BU)) : 0u; }
+
+// One round.  n_in undecided points: the sorted positions list_in[0 .. n_in), or 0 .. n_in itself when list_in is null
+// (round 1: every sorted point).  Cells are numbered x fastest: the cells x0 .. x1 of one (y, z) row are one contiguous
+// range of sorted records, as in cloud::search_kernel.
+__global__ __launch_bounds__(kBlock) void round_kernel(const Rec *__restrict__ sorted, const uint32_t *__restrict__ ends, Grid g, float reach,
+                                                       uint32_t salt, int hashed, uint32_t round, uint32_t *state,
+                                                       const uint32_t *__restrict__ list_in, uint32_t n_in,
+                                                       uint32_t *__restrict__ list_out, uint32_t *__restrict__ counters,
+                                                       uint8_t *__restrict__ keep)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    bool kept = false, survives = false;
+    uint32_t pos = 0;
+    if (t < n_in) {
+        pos = list_in ? list_in[t] : t;
+        const Rec a = sorted[pos];
+        const uint32_t pa = prio_of(a.j, salt, hashed);
+        const int x0 = cell_of(a.x - reach, g.lo[0], g.inv_h, g.g[0]), x1 = cell_of(a.x + reach, g.lo[0], g.inv_h, g.g[0]);
+        const int y0 = cell_of(a.y - reach, g.lo[1], g.inv_h, g.g[1]), y1 = cell_of(a.y + reach, g.lo[1], g.inv_h, g.g[1]);
+        const int z0 = cell_of(a.z - reach, g.lo[2], g.inv_h, g.g[2]), z1 = cell_of(a.z + reach, g.lo[2], g.inv_h, g.g[2]);
+        bool dropped = false, blocked = false;
+        for (int z = z0; z <= z1 && !dropped; ++z)
+            for (int y = y0; y <= y1 && !dropped; ++y) {
+                const int c0 = (z * g.g[1] + y) * g.g[0] + x0, c1 = c0 + (x1 - x0);
+                const uint32_t end = ends[c1];
+                for (uint32_t p = c0 ? ends[c0 - 1] : 0u; p < end; ++p) {
+                    const Rec b = sorted[p];
+                    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (!(d2 <= g.r2) || p == pos) continue;
+                    const uint32_t pb = prio_of(b.j, salt, hashed);
+                    if (!(pb < pa || (pb == pa && b.j < a.j))) continue;  // (only lower keys decide about a)
+                    const uint32_t s = state[p];
+                    if (s == 0u || (s >> 1) >= round) {
+                        blocked = true;  // undecided, or decided in this very round
+                    } else if (s & 1u) {
+                        dropped = true;
+                        break;
+                    }
+                }
+            }
+        kept = !dropped && !blocked;
+        survives = !dropped && blocked;
+        if (!survives) state[pos] = 2u * round + (kept ? 1u : 0u);
+        if (kept) keep[a.j] = 1;  // (the mask comes in cleared)
+    }
+    // the counters and the worklist: one atomic each per wavefront (integer sums; the list's order is free)
+    const uint64_t bk = __ballot(kept), bs = __ballot(survives);
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t base = 0;
+    if (lane == 0) {
+        if (bk) atomicAdd(&counters[kKept], (uint32_t)__popcll(bk));
+        if (bs) base = atomicAdd(&counters[kSurvivors], (uint32_t)__popcll(bs));
+    }
+    base = __shfl(base, 0);
+    if (survives) list_out[base + (uint32_t)__popcll(bs & ((1ull << lane) - 1ull))] = pos;
+}
+
+// The automatic G: a cell edge of about the radius -- never below it -- where 256 cells allow it, so that a lane's range
+// of 2.02 radii covers three, at most four, cells per axis; 256 where the radius is below 1/256 of the longest extent
+// (the cells then hold more than a neighbourhood; the result stays exact and the rounds get slower).  Reasoned, not
+// measured.
+inline int automatic_grid(float longest, float radius)
+{
+    const double q = (double)longest / (double)radius;
+    return q >= (double)cloud::kMaxGrid ? cloud::kMaxGrid : q < 1.0 ? 1 : (int)q;
+}
+
+}  // namespace thin
+
 namespace {
 
 thread_local int64_t last_stats[6] = {0, 0, 0, 0, 0, 0};  // gipuma_hip_cloud_last_stats
@@ -462,6 +596,146 @@ int run(const gipuma_hip_cloud_desc *d, float *d2_dev, int32_t *idx_dev, int64_t
     return 0;
 }
 
+
+// the scratch of gipuma_hip_cloud_thin: freed on every way out
+struct ThinScratch {
+    float *partial = nullptr, *box = nullptr;
+    uint32_t *cells = nullptr, *counters = nullptr, *state = nullptr, *list[2] = {nullptr, nullptr};
+    int32_t *cellid = nullptr;
+    cloud::Rec *sorted = nullptr;
+    hipStream_t st = nullptr, own = nullptr;
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~ThinScratch()
+    {
+        if (st) (void)hipStreamSynchronize(st);  // (nothing of this call is in flight when its buffers go)
+        (void)hipFree(partial);
+        (void)hipFree(box);
+        (void)hipFree(cells);
+        (void)hipFree(counters);
+        (void)hipFree(state);
+        (void)hipFree(list[0]);
+        (void)hipFree(list[1]);
+        (void)hipFree(cellid);
+        (void)hipFree(sorted);
+        for (hipEvent_t ev : e)
+            if (ev) (void)hipEventDestroy(ev);
+        if (own) (void)hipStreamDestroy(own);
+    }
+};
+
+int run_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int64_t info[8], float *device_ms)
+{
+    using namespace cloud;
+    const uint32_t n = (uint32_t)d->n_points;
+    HIP_OK(hipSetDevice(d->device_id));
+    ThinScratch sc;
+    if (d->stream) {
+        sc.st = (hipStream_t)d->stream;
+    } else {
+        HIP_OK(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
+        sc.st = sc.own;
+    }
+    hipStream_t st = sc.st;
+    for (hipEvent_t &ev : sc.e) HIP_OK(hipEventCreate(&ev));
+    const dim3 block(kBlock);
+    int64_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kept, dropped, not finite, rounds, G, cells x, y, z
+    float ms = 0.f;
+
+    if (n) {
+        // the mask comes out of the rounds with the kept points set; the box of the finite points
+        float box[6];
+        const int nblocks = (int)(blocks_for(n).x < (uint32_t)kBoxBlocks ? blocks_for(n).x : (uint32_t)kBoxBlocks);
+        HIP_OK(hipMalloc(&sc.partial, sizeof(float) * 6 * nblocks));
+        HIP_OK(hipMalloc(&sc.box, sizeof box));
+        HIP_OK(hipEventRecord(sc.e[0], st));
+        HIP_OK(hipMemsetAsync(keep_dev, 0, n, st));
+        hipLaunchKernelGGL(box_partial_kernel, dim3(nblocks), block, 0, st, d->points, n, sc.partial);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(box_final_kernel, dim3(1), block, 0, st, sc.partial, nblocks, sc.box);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(box, sc.box, sizeof box, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+
+        uint32_t finite = 0, kept = 0, rounds = 0;
+        if (box[0] <= box[3] && box[1] <= box[4] && box[2] <= box[5]) {  // (else: no finite point, nothing is kept)
+            // the grid, laid out as the search's: one cell edge h, G cells along the longest axis, one for a zero extent
+            Grid g;
+            float ext[3], longest = 0.f;
+            for (int k = 0; k < 3; ++k) {
+                g.lo[k] = box[k];
+                g.hi[k] = box[3 + k];
+                ext[k] = box[3 + k] - box[k];
+                longest = fmaxf(longest, ext[k]);
+            }
+            g.r2 = d->radius * d->radius;
+            int G = d->grid ? d->grid : thin::automatic_grid(longest, d->radius);
+            g.h = longest / (float)G;
+            // one cell -- every point visited -- where the derivation of thin::kReach does not hold: radius or h outside
+            // 2^-40 .. 2^40, an infinite extent
+            if (!(g.h >= 0x1p-40f && g.h <= 0x1p40f) || !(d->radius >= 0x1p-40f && d->radius <= 0x1p40f)) G = 1;
+            if (G == 1) g.h = 1.f;
+            g.inv_h = 1.f / g.h;
+            for (int k = 0; k < 3; ++k) {
+                const int cells = G == 1 || !(ext[k] > 0.f) ? 1 : (int)floorf(ext[k] * g.inv_h) + 1;
+                g.g[k] = cells < 1 ? 1 : cells > G ? G : cells;
+            }
+            const uint32_t ncells = (uint32_t)g.g[0] * g.g[1] * g.g[2];
+            out[4] = G;
+            for (int k = 0; k < 3; ++k) out[5 + k] = g.g[k];
+
+            HIP_OK(hipMalloc(&sc.cells, sizeof(uint32_t) * ncells));
+            HIP_OK(hipMalloc(&sc.counters, sizeof(uint32_t) * thin::kCounters));
+            HIP_OK(hipMalloc(&sc.cellid, sizeof(int32_t) * n));
+            HIP_OK(hipMalloc(&sc.sorted, sizeof(Rec) * n));
+            HIP_OK(hipMalloc(&sc.state, sizeof(uint32_t) * n));
+            HIP_OK(hipMalloc(&sc.list[0], sizeof(uint32_t) * n));
+            HIP_OK(hipMalloc(&sc.list[1], sizeof(uint32_t) * n));
+            HIP_OK(hipMemsetAsync(sc.cells, 0, sizeof(uint32_t) * ncells, st));
+            HIP_OK(hipMemsetAsync(sc.counters, 0, sizeof(uint32_t) * thin::kCounters, st));
+            HIP_OK(hipMemsetAsync(sc.state, 0, sizeof(uint32_t) * n, st));
+            hipLaunchKernelGGL(count_kernel<false>, blocks_for(n), block, 0, st, d->points, n, g, sc.cellid, sc.cells, (float *)nullptr,
+                               (int32_t *)nullptr, sc.counters);
+            HIP_OK(hipGetLastError());
+            hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScan), 0, st, sc.cells, ncells, (uint32_t *)nullptr);
+            HIP_OK(hipGetLastError());
+            hipLaunchKernelGGL(scatter_kernel, blocks_for(n), block, 0, st, d->points, n, sc.cellid, sc.cells, sc.sorted);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipMemcpyAsync(&finite, sc.counters + kTargets, sizeof finite, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+
+            // the rounds: the host reads the survivor count after each and sizes the next launch with it
+            const float reach = thin::kReach * d->radius;
+            const uint32_t salt = thin::mix32(d->seed + 0x9E3779B9U);
+            uint32_t undecided = finite;
+            while (undecided) {
+                ++rounds;
+                uint32_t survivors = 0;
+                HIP_OK(hipMemsetAsync(sc.counters + thin::kSurvivors, 0, sizeof(uint32_t), st));
+                hipLaunchKernelGGL(thin::round_kernel, blocks_for(undecided), block, 0, st, sc.sorted, sc.cells, g, reach, salt,
+                                   d->order == 0 ? 1 : 0, rounds, sc.state, rounds == 1 ? (const uint32_t *)nullptr : sc.list[rounds & 1],
+                                   undecided, sc.list[(rounds + 1) & 1], sc.counters, keep_dev);
+                HIP_OK(hipGetLastError());
+                HIP_OK(hipMemcpyAsync(&survivors, sc.counters + thin::kSurvivors, sizeof survivors, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipStreamSynchronize(st));
+                if (survivors >= undecided)  // (the lowest-key undecided point is always decided: this bounds the loop)
+                    return fail(GIPUMA_HIP_ERR_DEVICE, "thin: round %u decided none of its %u undecided points", rounds, undecided);
+                undecided = survivors;
+            }
+            HIP_OK(hipMemcpyAsync(&kept, sc.counters + thin::kKept, sizeof kept, hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipEventRecord(sc.e[1], st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(&ms, sc.e[0], sc.e[1]));
+        out[0] = kept;
+        out[1] = (int64_t)finite - kept;
+        out[2] = (int64_t)n - finite;
+        out[3] = rounds;
+    }
+    if (info) memcpy(info, out, sizeof out);
+    if (device_ms) *device_ms = ms;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -487,6 +761,20 @@ int gipuma_hip_cloud_last_stats(int64_t stats[6])
     if (!stats) return fail(GIPUMA_HIP_ERR_ARG, "null argument");
     memcpy(stats, last_stats, sizeof last_stats);
     return 0;
+}
+
+int gipuma_hip_cloud_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int64_t info[8], float *device_ms)
+{
+    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
+    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "thin: abi_version mismatch");
+    if (d->n_points < 0) return fail(GIPUMA_HIP_ERR_ARG, "thin: negative point count");
+    if (d->n_points >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "thin: a cloud may hold at most 2^31 - 1 points");
+    if (d->n_points && (!d->points || !keep_dev)) return fail(GIPUMA_HIP_ERR_ARG, "thin: null pointer with a non-zero point count");
+    if (!(d->radius > 0.f) || !std::isfinite(d->radius)) return fail(GIPUMA_HIP_ERR_ARG, "thin: radius must be > 0 and finite");
+    if (d->order != 0 && d->order != 1) return fail(GIPUMA_HIP_ERR_ARG, "thin: order must be 0 (hashed) or 1 (index)");
+    if (d->grid < 0 || d->grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "thin: grid must be 0 (automatic) or 1..256");
+    if (const int rc = pm_host::check_device(d->device_id)) return rc;
+    return run_thin(d, keep_dev, info, device_ms);
 }
 
 }  // extern "C"

@@ -402,6 +402,41 @@ int gipuma_hip_cloud_nearest(const gipuma_hip_cloud_desc *desc, float *d2_dev, i
  * queries searched.  All 0 after a call that had no finite target or no query. */
 int gipuma_hip_cloud_last_stats(int64_t stats[6]);
 
+/* ---- thinning a cloud to a minimum point spacing: the density normalisation before the score ----
+ * P: n_points packed float32 xyz.  d2(i, j) is gipuma_hip_cloud_nearest's, float32 without contraction, and bitwise
+ * symmetric in i, j (negation is exact); r2 = radius * radius in float32; the radius is inclusive.
+ *     key(i) = (prio(i), i), compared lexicographically, lower first
+ *     order 0 (hashed): prio(i) = mix32(mix32(seed + 0x9E3779B9u) ^ ((uint32_t)i + 0x85EBCA6Bu)), uint32 wrap-around,
+ *                       mix32(h): h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16
+ *     order 1 (index):  prio(i) = 0 -- the caller's own order
+ *     a point that is not finite in all three coordinates is never kept and never suppresses another point
+ *     the finite points are visited in ascending key;  i is KEPT  iff  no point kept before it has d2(i, j) <= r2
+ *     keep_dev[i] = 1 for a kept point, 0 for any other
+ * This is the lexicographically first maximal independent set of the radius graph: kept points are pairwise d2 > r2,
+ * every finite dropped point has a kept point of lower key within the radius, and the mask is a pure function of
+ * (P, radius, seed, order) -- defined without reference to the grid or to the rounds the kernels decide it in, and equal
+ * to the sequential pass in every byte (tests/thin_ref.py).  `grid` (cells along the longest axis of the finite points'
+ * box) changes the time only; 0 lets the library choose a cell edge of about the radius, at most 256 cells.
+ * n_points = 0 writes nothing and reports 0 rounds.  Blocks until the mask is complete; the cloud must be complete on
+ * desc->stream's terms when the call is made.  Scratch (about 32 bytes per point and 4 per cell) is allocated for the
+ * call and freed before it returns, on every error path too. */
+typedef struct gipuma_hip_thin_desc {
+    uint32_t abi_version; /* GIPUMA_HIP_ABI_VERSION */
+    int64_t n_points;     /* < 2^31; more: GIPUMA_HIP_ERR_UNSUPPORTED */
+    const float *points;  /* device pointer, packed xyz float32 */
+    float radius;         /* > 0 and finite, else GIPUMA_HIP_ERR_ARG */
+    uint32_t seed;        /* of the hashed order */
+    int32_t order;        /* 0: hashed, 1: index */
+    int32_t grid;         /* 0: automatic; 1..256: cells along the longest axis */
+    int32_t device_id;    /* HIP device ordinal */
+    void *stream;         /* hipStream_t to launch on, NULL = one the library creates for the call */
+} gipuma_hip_thin_desc;
+
+/* keep_dev: n_points bytes, device.  info (points kept, finite points dropped, points not finite, rounds, cells along the
+ * longest axis, cells along x, y and z) and device_ms (HIP events around everything the call enqueues, the host's reads
+ * of the per-round survivor count included) may be NULL. */
+int gipuma_hip_cloud_thin(const gipuma_hip_thin_desc *desc, uint8_t *keep_dev, int64_t info[8], float *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
