@@ -25,12 +25,16 @@
 // lexicographically, and a cell's points are all visited or all skipped.
 //
 // The same grid has a second client: thinning a cloud to a minimum point spacing (namespace thin below, DESIGN.md 15,
-// gipuma_hip_cloud_thin), the density normalisation that comes before the score.
+// gipuma_hip_cloud_thin), the density normalisation that comes before the score.  What both clients do to get the grid
+// is written once, as the host steps at the end of namespace cloud: cloud::Box (the box of a cloud), cloud::lay_out (the
+// grid over a box) and cloud::sort_by_cell (the counting sort).  The exactness arguments of both rest on that one
+// layout: a monotonic cell_of, cells numbered x fastest, ends[] as the scatter leaves them.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
+#include "pm_hash.h"
 #include "pm_host.h"
 
 using pm_host::fail;
@@ -316,6 +320,92 @@ inline int automatic_grid(int64_t n_targets)
     return g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The host steps that build the grid, shared by the search and the thinning.  They enqueue on the caller's stream, record
+// no events and allocate only where the name says so: the callers place their timed windows around them.
+// ---------------------------------------------------------------------------------------------------------------------
+inline dim3 blocks_for(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
+
+// The box of a cloud's finite points.  enqueue() and read() are two calls, so that a caller may record an event between
+// the kernels and the host's read.
+struct Box {
+    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};  // lo[3], hi[3]; this where no point is finite
+    float *partial = nullptr, *dev = nullptr;
+    int nblocks = 0;
+
+    int alloc(pm_host::CallScope &sc, uint32_t n)
+    {
+        nblocks = (int)(blocks_for(n).x < (uint32_t)kBoxBlocks ? blocks_for(n).x : (uint32_t)kBoxBlocks);
+        return sc.alloc(partial, 6 * (size_t)nblocks) || sc.alloc(dev, 6) ? GIPUMA_HIP_ERR_DEVICE : 0;
+    }
+    int enqueue(hipStream_t st, const float *pts, uint32_t n) const
+    {
+        hipLaunchKernelGGL(box_partial_kernel, dim3(nblocks), dim3(kBlock), 0, st, pts, n, partial);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(box_final_kernel, dim3(1), dim3(kBlock), 0, st, partial, nblocks, dev);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+    int read(hipStream_t st)  // (one host read)
+    {
+        HIP_OK(hipMemcpyAsync(v, dev, sizeof v, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return 0;
+    }
+    bool any_finite() const { return v[0] <= v[3] && v[1] <= v[4] && v[2] <= v[5]; }
+    float longest_extent() const { return fmaxf(fmaxf(fmaxf(0.f, v[3] - v[0]), v[4] - v[1]), v[5] - v[2]); }
+};
+
+// The grid over a box: one cell edge h for all axes, G cells along the longest one; an axis of zero extent gets one cell.
+// One cell (G = 1: every point visited, the brute force) where a client's shortcut is not proven: h outside 2^-40 .. 2^40
+// (squares would underflow or overflow; an infinite extent ends up here), or the client says that its own derivation does
+// not hold (`shortcut_holds`: the search's kShellSlack wants a finite r2, the thinning's kReach a radius in that range).
+struct Layout {
+    Grid g;
+    uint32_t ncells;
+    int64_t report[4];  // G and the cells along x, y, z, as last_stats[0 .. 3] and the thinning's info[4 .. 7] report them
+};
+inline Layout lay_out(const Box &box, int G, float r2, bool shortcut_holds)
+{
+    Layout l;
+    Grid &g = l.g;
+    float ext[3];
+    for (int k = 0; k < 3; ++k) {
+        g.lo[k] = box.v[k];
+        g.hi[k] = box.v[3 + k];
+        ext[k] = box.v[3 + k] - box.v[k];
+    }
+    g.r2 = r2;
+    g.h = box.longest_extent() / (float)G;
+    if (!(g.h >= 0x1p-40f && g.h <= 0x1p40f) || !shortcut_holds) G = 1;
+    if (G == 1) g.h = 1.f;
+    g.inv_h = 1.f / g.h;
+    for (int k = 0; k < 3; ++k) {
+        const int cells = G == 1 || !(ext[k] > 0.f) ? 1 : (int)floorf(ext[k] * g.inv_h) + 1;
+        g.g[k] = cells < 1 ? 1 : cells > G ? G : cells;
+    }
+    l.ncells = (uint32_t)g.g[0] * g.g[1] * g.g[2];
+    l.report[0] = G;
+    for (int k = 0; k < 3; ++k) l.report[1 + k] = g.g[k];
+    return l;
+}
+
+// The counting sort of a cloud by cell: histogram, exclusive scan, scatter.  cells[ncells] comes in ZEROED (the caller's
+// memset, wherever on the stream it stands) and goes out as the cells' ends; cellid[n] and sorted[n] are scratch and
+// result.  kQuery, out_d2, out_idx: count_kernel's; *total = the number of sorted points when asked for.
+template <bool kQuery>
+int sort_by_cell(hipStream_t st, const float *pts, uint32_t n, const Layout &l, int32_t *cellid, uint32_t *cells, Rec *sorted,
+                 float *out_d2, int32_t *out_idx, uint32_t *stats, uint32_t *total)
+{
+    hipLaunchKernelGGL(count_kernel<kQuery>, blocks_for(n), dim3(kBlock), 0, st, pts, n, l.g, cellid, cells, out_d2, out_idx, stats);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScan), 0, st, cells, l.ncells, total);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(scatter_kernel, blocks_for(n), dim3(kBlock), 0, st, pts, n, cellid, cells, sorted);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 }  // namespace cloud
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -326,7 +416,8 @@ inline int automatic_grid(int64_t n_targets)
 //
 // Launches, all on one stream:
 //   cloud::box_*, count_kernel<false>, scan_kernel, scatter_kernel    the box of the finite points and their counting sort
-//                                                  by cell, once, exactly as for the search's targets
+//                                                  by cell, once, through the steps the search takes for its targets:
+//                                                  cloud::Box, cloud::lay_out, cloud::sort_by_cell<false>
 //   thin::round_kernel, once per round t = 1, 2, ...   one lane per UNDECIDED point, taken from a worklist of sorted
 //                                                  positions; survivors are appended to the other worklist (one ballot
 //                                                  and one atomicAdd per wavefront); the host reads the 4-byte survivor
@@ -368,16 +459,7 @@ enum { kKept = cloud::kStats, kSurvivors, kCounters };  // the device counters, 
 constexpr float kReach = 1.01f;
 
 // prio(i) of the hashed order: mix32(mix32(seed + 0x9E3779B9) ^ (i + 0x85EBCA6B)); salt is the inner mix32, from the host.
-// (mix32 is pm_core.h's, restated: that header would bring the solver's pack kernels into this unit.)
-__host__ __device__ __forceinline__ uint32_t mix32(uint32_t h)
-{
-    h ^= h >> 16;
-    h *= 0x7feb352dU;
-    h ^= h >> 15;
-    h *= 0x846ca68bU;
-    h ^= h >> 16;
-    return h;
-}
+using pm::mix32;
 __device__ __forceinline__ uint32_t prio_of(int32_t i, uint32_t salt, bool hashed) { return hashed ? mix32(salt ^ ((uint32_t)i + 0x85EBCA6BU)) : 0u; }
 
 // One round.  n_in undecided points: the sorted positions list_in[0 .. n_in), or 0 .. n_in itself when list_in is null
@@ -453,140 +535,68 @@ namespace {
 
 thread_local int64_t last_stats[6] = {0, 0, 0, 0, 0, 0};  // gipuma_hip_cloud_last_stats
 
-// the call's scratch: freed on every way out of gipuma_hip_cloud_nearest
-struct Scratch {
-    float *partial = nullptr, *box = nullptr;
-    uint32_t *cells_b = nullptr, *cells_a = nullptr, *stats = nullptr;
-    int32_t *cellid_b = nullptr, *cellid_a = nullptr;
-    cloud::Rec *sorted_b = nullptr, *sorted_a = nullptr;
-    hipStream_t st = nullptr, own = nullptr;
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Scratch()
-    {
-        if (st) (void)hipStreamSynchronize(st);  // (nothing of this call is in flight when its buffers go)
-        (void)hipFree(partial);
-        (void)hipFree(box);
-        (void)hipFree(cells_b);
-        (void)hipFree(cells_a);
-        (void)hipFree(stats);
-        (void)hipFree(cellid_b);
-        (void)hipFree(cellid_a);
-        (void)hipFree(sorted_b);
-        (void)hipFree(sorted_a);
-        for (hipEvent_t ev : e)
-            if (ev) (void)hipEventDestroy(ev);
-        if (own) (void)hipStreamDestroy(own);
-    }
-};
-
-inline dim3 blocks_for(uint32_t n) { return dim3((n + cloud::kBlock - 1) / cloud::kBlock); }
-
 int run(const gipuma_hip_cloud_desc *d, float *d2_dev, int32_t *idx_dev, int64_t counts[2], float *device_ms)
 {
-    using namespace cloud;
     const uint32_t na = (uint32_t)d->n_queries, nb = (uint32_t)d->n_targets;
     HIP_OK(hipSetDevice(d->device_id));
-    Scratch sc;
-    if (d->stream) {
-        sc.st = (hipStream_t)d->stream;
-    } else {
-        HIP_OK(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
-        sc.st = sc.own;
-    }
+    pm_host::CallScope sc;
+    if (const int rc = sc.open(d->stream, 4)) return rc;
     hipStream_t st = sc.st;
-    for (hipEvent_t &ev : sc.e) HIP_OK(hipEventCreate(&ev));
-    const dim3 block(kBlock);
+    const dim3 block(cloud::kBlock);
     float ms_box = 0.f, ms_rest = 0.f;
     int64_t found = 0;
 
     // the box of the finite targets
-    float box[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    cloud::Box box;
     if (na && nb) {
-        const int nblocks = (int)(blocks_for(nb).x < (uint32_t)kBoxBlocks ? blocks_for(nb).x : (uint32_t)kBoxBlocks);
-        HIP_OK(hipMalloc(&sc.partial, sizeof(float) * 6 * nblocks));
-        HIP_OK(hipMalloc(&sc.box, sizeof box));
+        if (const int rc = box.alloc(sc, nb)) return rc;
         HIP_OK(hipEventRecord(sc.e[0], st));
-        hipLaunchKernelGGL(box_partial_kernel, dim3(nblocks), block, 0, st, d->targets, nb, sc.partial);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(box_final_kernel, dim3(1), block, 0, st, sc.partial, nblocks, sc.box);
-        HIP_OK(hipGetLastError());
+        if (const int rc = box.enqueue(st, d->targets, nb)) return rc;
         HIP_OK(hipEventRecord(sc.e[1], st));
-        HIP_OK(hipMemcpyAsync(box, sc.box, sizeof box, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
+        if (const int rc = box.read(st)) return rc;
         HIP_OK(hipEventElapsedTime(&ms_box, sc.e[0], sc.e[1]));
     }
-    const bool any_target = box[0] <= box[3] && box[1] <= box[4] && box[2] <= box[5];
 
-    if (na && !any_target) {
+    if (na && !box.any_finite()) {
         HIP_OK(hipEventRecord(sc.e[2], st));
-        hipLaunchKernelGGL(none_kernel, blocks_for(na), block, 0, st, na, d2_dev, idx_dev);
+        hipLaunchKernelGGL(cloud::none_kernel, cloud::blocks_for(na), block, 0, st, na, d2_dev, idx_dev);
         HIP_OK(hipGetLastError());
         HIP_OK(hipEventRecord(sc.e[3], st));
         HIP_OK(hipStreamSynchronize(st));
         HIP_OK(hipEventElapsedTime(&ms_rest, sc.e[2], sc.e[3]));
     } else if (na) {
-        // the grid: one cell edge h for all axes, G cells along the longest one; an axis of zero extent gets one cell
-        Grid g;
-        float ext[3], longest = 0.f;
-        for (int k = 0; k < 3; ++k) {
-            g.lo[k] = box[k];
-            g.hi[k] = box[3 + k];
-            ext[k] = box[3 + k] - box[k];
-            longest = fmaxf(longest, ext[k]);
-        }
-        g.r2 = d->max_dist * d->max_dist;
-        int G = d->grid ? d->grid : automatic_grid(d->n_targets);
-        g.h = longest / (float)G;
-        // one cell -- the brute force -- where the derivation of kShellSlack does not hold: h outside 2^-40 .. 2^40 (squares
-        // would underflow or overflow), an infinite extent or an infinite r2
-        if (!(g.h >= 0x1p-40f && g.h <= 0x1p40f) || !std::isfinite(g.r2)) G = 1;
-        if (G == 1) g.h = 1.f;
-        g.inv_h = 1.f / g.h;
-        for (int k = 0; k < 3; ++k) {
-            const int cells = G == 1 || !(ext[k] > 0.f) ? 1 : (int)floorf(ext[k] * g.inv_h) + 1;
-            g.g[k] = cells < 1 ? 1 : cells > G ? G : cells;
-        }
-        const uint32_t ncells = (uint32_t)g.g[0] * g.g[1] * g.g[2];
-        last_stats[0] = G;
-        for (int k = 0; k < 3; ++k) last_stats[1 + k] = g.g[k];
+        // the grid; the derivation of kShellSlack does not hold for an infinite r2
+        const float r2 = d->max_dist * d->max_dist;
+        const cloud::Layout l = cloud::lay_out(box, d->grid ? d->grid : cloud::automatic_grid(d->n_targets), r2, std::isfinite(r2));
+        for (int k = 0; k < 4; ++k) last_stats[k] = l.report[k];
 
-        HIP_OK(hipMalloc(&sc.cells_b, sizeof(uint32_t) * ncells));
-        HIP_OK(hipMalloc(&sc.cells_a, sizeof(uint32_t) * ncells));
-        HIP_OK(hipMalloc(&sc.stats, sizeof(uint32_t) * kStats));
-        HIP_OK(hipMalloc(&sc.cellid_b, sizeof(int32_t) * nb));
-        HIP_OK(hipMalloc(&sc.cellid_a, sizeof(int32_t) * na));
-        HIP_OK(hipMalloc(&sc.sorted_b, sizeof(Rec) * nb));
-        HIP_OK(hipMalloc(&sc.sorted_a, sizeof(Rec) * na));
+        uint32_t *cells_b, *cells_a, *stats_dev;
+        int32_t *cellid_b, *cellid_a;
+        cloud::Rec *sorted_b, *sorted_a;
+        if (sc.alloc(cells_b, l.ncells) || sc.alloc(cells_a, l.ncells) || sc.alloc(stats_dev, cloud::kStats) || sc.alloc(cellid_b, nb) ||
+            sc.alloc(cellid_a, na) || sc.alloc(sorted_b, nb) || sc.alloc(sorted_a, na))
+            return GIPUMA_HIP_ERR_DEVICE;
 
         HIP_OK(hipEventRecord(sc.e[2], st));
-        HIP_OK(hipMemsetAsync(sc.cells_b, 0, sizeof(uint32_t) * ncells, st));
-        HIP_OK(hipMemsetAsync(sc.cells_a, 0, sizeof(uint32_t) * ncells, st));
-        HIP_OK(hipMemsetAsync(sc.stats, 0, sizeof(uint32_t) * kStats, st));
-        hipLaunchKernelGGL(count_kernel<false>, blocks_for(nb), block, 0, st, d->targets, nb, g, sc.cellid_b, sc.cells_b,
-                           (float *)nullptr, (int32_t *)nullptr, sc.stats);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScan), 0, st, sc.cells_b, ncells, (uint32_t *)nullptr);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(scatter_kernel, blocks_for(nb), block, 0, st, d->targets, nb, sc.cellid_b, sc.cells_b, sc.sorted_b);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(count_kernel<true>, blocks_for(na), block, 0, st, d->queries, na, g, sc.cellid_a, sc.cells_a, d2_dev,
-                           idx_dev, sc.stats);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScan), 0, st, sc.cells_a, ncells, sc.stats + kSearched);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(scatter_kernel, blocks_for(na), block, 0, st, d->queries, na, sc.cellid_a, sc.cells_a, sc.sorted_a);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(search_kernel, blocks_for(na), block, 0, st, sc.sorted_a, sc.stats + kSearched, sc.sorted_b, sc.cells_b, g,
-                           d2_dev, idx_dev, sc.stats);
+        HIP_OK(hipMemsetAsync(cells_b, 0, sizeof(uint32_t) * l.ncells, st));
+        HIP_OK(hipMemsetAsync(cells_a, 0, sizeof(uint32_t) * l.ncells, st));
+        HIP_OK(hipMemsetAsync(stats_dev, 0, sizeof(uint32_t) * cloud::kStats, st));
+        if (const int rc = cloud::sort_by_cell<false>(st, d->targets, nb, l, cellid_b, cells_b, sorted_b, nullptr, nullptr, stats_dev, nullptr))
+            return rc;
+        if (const int rc = cloud::sort_by_cell<true>(st, d->queries, na, l, cellid_a, cells_a, sorted_a, d2_dev, idx_dev, stats_dev,
+                                                     stats_dev + cloud::kSearched))
+            return rc;
+        hipLaunchKernelGGL(cloud::search_kernel, cloud::blocks_for(na), block, 0, st, sorted_a, stats_dev + cloud::kSearched, sorted_b,
+                           cells_b, l.g, d2_dev, idx_dev, stats_dev);
         HIP_OK(hipGetLastError());
         HIP_OK(hipEventRecord(sc.e[3], st));
-        uint32_t stats[kStats];
-        HIP_OK(hipMemcpyAsync(stats, sc.stats, sizeof stats, hipMemcpyDeviceToHost, st));
+        uint32_t stats[cloud::kStats];
+        HIP_OK(hipMemcpyAsync(stats, stats_dev, sizeof stats, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         HIP_OK(hipEventElapsedTime(&ms_rest, sc.e[2], sc.e[3]));
-        found = stats[kFound];
-        last_stats[4] = stats[kEarly];
-        last_stats[5] = stats[kSearched];
+        found = stats[cloud::kFound];
+        last_stats[4] = stats[cloud::kEarly];
+        last_stats[5] = stats[cloud::kSearched];
     }
     if (counts) {
         counts[0] = found;
@@ -596,132 +606,65 @@ int run(const gipuma_hip_cloud_desc *d, float *d2_dev, int32_t *idx_dev, int64_t
     return 0;
 }
 
-
-// the scratch of gipuma_hip_cloud_thin: freed on every way out
-struct ThinScratch {
-    float *partial = nullptr, *box = nullptr;
-    uint32_t *cells = nullptr, *counters = nullptr, *state = nullptr, *list[2] = {nullptr, nullptr};
-    int32_t *cellid = nullptr;
-    cloud::Rec *sorted = nullptr;
-    hipStream_t st = nullptr, own = nullptr;
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~ThinScratch()
-    {
-        if (st) (void)hipStreamSynchronize(st);  // (nothing of this call is in flight when its buffers go)
-        (void)hipFree(partial);
-        (void)hipFree(box);
-        (void)hipFree(cells);
-        (void)hipFree(counters);
-        (void)hipFree(state);
-        (void)hipFree(list[0]);
-        (void)hipFree(list[1]);
-        (void)hipFree(cellid);
-        (void)hipFree(sorted);
-        for (hipEvent_t ev : e)
-            if (ev) (void)hipEventDestroy(ev);
-        if (own) (void)hipStreamDestroy(own);
-    }
-};
-
 int run_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int64_t info[8], float *device_ms)
 {
-    using namespace cloud;
     const uint32_t n = (uint32_t)d->n_points;
     HIP_OK(hipSetDevice(d->device_id));
-    ThinScratch sc;
-    if (d->stream) {
-        sc.st = (hipStream_t)d->stream;
-    } else {
-        HIP_OK(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
-        sc.st = sc.own;
-    }
+    pm_host::CallScope sc;
+    if (const int rc = sc.open(d->stream, 2)) return rc;
     hipStream_t st = sc.st;
-    for (hipEvent_t &ev : sc.e) HIP_OK(hipEventCreate(&ev));
-    const dim3 block(kBlock);
     int64_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kept, dropped, not finite, rounds, G, cells x, y, z
     float ms = 0.f;
 
     if (n) {
         // the mask comes out of the rounds with the kept points set; the box of the finite points
-        float box[6];
-        const int nblocks = (int)(blocks_for(n).x < (uint32_t)kBoxBlocks ? blocks_for(n).x : (uint32_t)kBoxBlocks);
-        HIP_OK(hipMalloc(&sc.partial, sizeof(float) * 6 * nblocks));
-        HIP_OK(hipMalloc(&sc.box, sizeof box));
+        cloud::Box box;
+        if (const int rc = box.alloc(sc, n)) return rc;
         HIP_OK(hipEventRecord(sc.e[0], st));
         HIP_OK(hipMemsetAsync(keep_dev, 0, n, st));
-        hipLaunchKernelGGL(box_partial_kernel, dim3(nblocks), block, 0, st, d->points, n, sc.partial);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(box_final_kernel, dim3(1), block, 0, st, sc.partial, nblocks, sc.box);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(box, sc.box, sizeof box, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
+        if (const int rc = box.enqueue(st, d->points, n)) return rc;
+        if (const int rc = box.read(st)) return rc;
 
         uint32_t finite = 0, kept = 0, rounds = 0;
-        if (box[0] <= box[3] && box[1] <= box[4] && box[2] <= box[5]) {  // (else: no finite point, nothing is kept)
-            // the grid, laid out as the search's: one cell edge h, G cells along the longest axis, one for a zero extent
-            Grid g;
-            float ext[3], longest = 0.f;
-            for (int k = 0; k < 3; ++k) {
-                g.lo[k] = box[k];
-                g.hi[k] = box[3 + k];
-                ext[k] = box[3 + k] - box[k];
-                longest = fmaxf(longest, ext[k]);
-            }
-            g.r2 = d->radius * d->radius;
-            int G = d->grid ? d->grid : thin::automatic_grid(longest, d->radius);
-            g.h = longest / (float)G;
-            // one cell -- every point visited -- where the derivation of thin::kReach does not hold: radius or h outside
-            // 2^-40 .. 2^40, an infinite extent
-            if (!(g.h >= 0x1p-40f && g.h <= 0x1p40f) || !(d->radius >= 0x1p-40f && d->radius <= 0x1p40f)) G = 1;
-            if (G == 1) g.h = 1.f;
-            g.inv_h = 1.f / g.h;
-            for (int k = 0; k < 3; ++k) {
-                const int cells = G == 1 || !(ext[k] > 0.f) ? 1 : (int)floorf(ext[k] * g.inv_h) + 1;
-                g.g[k] = cells < 1 ? 1 : cells > G ? G : cells;
-            }
-            const uint32_t ncells = (uint32_t)g.g[0] * g.g[1] * g.g[2];
-            out[4] = G;
-            for (int k = 0; k < 3; ++k) out[5 + k] = g.g[k];
+        if (box.any_finite()) {  // (else: nothing is kept)
+            // the grid; the derivation of thin::kReach does not hold for a radius outside 2^-40 .. 2^40
+            const cloud::Layout l = cloud::lay_out(box, d->grid ? d->grid : thin::automatic_grid(box.longest_extent(), d->radius),
+                                                   d->radius * d->radius, d->radius >= 0x1p-40f && d->radius <= 0x1p40f);
+            memcpy(out + 4, l.report, sizeof l.report);
 
-            HIP_OK(hipMalloc(&sc.cells, sizeof(uint32_t) * ncells));
-            HIP_OK(hipMalloc(&sc.counters, sizeof(uint32_t) * thin::kCounters));
-            HIP_OK(hipMalloc(&sc.cellid, sizeof(int32_t) * n));
-            HIP_OK(hipMalloc(&sc.sorted, sizeof(Rec) * n));
-            HIP_OK(hipMalloc(&sc.state, sizeof(uint32_t) * n));
-            HIP_OK(hipMalloc(&sc.list[0], sizeof(uint32_t) * n));
-            HIP_OK(hipMalloc(&sc.list[1], sizeof(uint32_t) * n));
-            HIP_OK(hipMemsetAsync(sc.cells, 0, sizeof(uint32_t) * ncells, st));
-            HIP_OK(hipMemsetAsync(sc.counters, 0, sizeof(uint32_t) * thin::kCounters, st));
-            HIP_OK(hipMemsetAsync(sc.state, 0, sizeof(uint32_t) * n, st));
-            hipLaunchKernelGGL(count_kernel<false>, blocks_for(n), block, 0, st, d->points, n, g, sc.cellid, sc.cells, (float *)nullptr,
-                               (int32_t *)nullptr, sc.counters);
-            HIP_OK(hipGetLastError());
-            hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kScan), 0, st, sc.cells, ncells, (uint32_t *)nullptr);
-            HIP_OK(hipGetLastError());
-            hipLaunchKernelGGL(scatter_kernel, blocks_for(n), block, 0, st, d->points, n, sc.cellid, sc.cells, sc.sorted);
-            HIP_OK(hipGetLastError());
-            HIP_OK(hipMemcpyAsync(&finite, sc.counters + kTargets, sizeof finite, hipMemcpyDeviceToHost, st));
+            uint32_t *cells, *counters, *state, *list[2];
+            int32_t *cellid;
+            cloud::Rec *sorted;
+            if (sc.alloc(cells, l.ncells) || sc.alloc(counters, thin::kCounters) || sc.alloc(cellid, n) || sc.alloc(sorted, n) ||
+                sc.alloc(state, n) || sc.alloc(list[0], n) || sc.alloc(list[1], n))
+                return GIPUMA_HIP_ERR_DEVICE;
+            HIP_OK(hipMemsetAsync(cells, 0, sizeof(uint32_t) * l.ncells, st));
+            HIP_OK(hipMemsetAsync(counters, 0, sizeof(uint32_t) * thin::kCounters, st));
+            HIP_OK(hipMemsetAsync(state, 0, sizeof(uint32_t) * n, st));
+            if (const int rc = cloud::sort_by_cell<false>(st, d->points, n, l, cellid, cells, sorted, nullptr, nullptr, counters, nullptr))
+                return rc;
+            HIP_OK(hipMemcpyAsync(&finite, counters + cloud::kTargets, sizeof finite, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
 
             // the rounds: the host reads the survivor count after each and sizes the next launch with it
             const float reach = thin::kReach * d->radius;
-            const uint32_t salt = thin::mix32(d->seed + 0x9E3779B9U);
+            const uint32_t salt = pm::mix32(d->seed + 0x9E3779B9U);
             uint32_t undecided = finite;
             while (undecided) {
                 ++rounds;
                 uint32_t survivors = 0;
-                HIP_OK(hipMemsetAsync(sc.counters + thin::kSurvivors, 0, sizeof(uint32_t), st));
-                hipLaunchKernelGGL(thin::round_kernel, blocks_for(undecided), block, 0, st, sc.sorted, sc.cells, g, reach, salt,
-                                   d->order == 0 ? 1 : 0, rounds, sc.state, rounds == 1 ? (const uint32_t *)nullptr : sc.list[rounds & 1],
-                                   undecided, sc.list[(rounds + 1) & 1], sc.counters, keep_dev);
+                HIP_OK(hipMemsetAsync(counters + thin::kSurvivors, 0, sizeof(uint32_t), st));
+                hipLaunchKernelGGL(thin::round_kernel, cloud::blocks_for(undecided), dim3(cloud::kBlock), 0, st, sorted, cells, l.g, reach,
+                                   salt, d->order == 0 ? 1 : 0, rounds, state, rounds == 1 ? (const uint32_t *)nullptr : list[rounds & 1],
+                                   undecided, list[(rounds + 1) & 1], counters, keep_dev);
                 HIP_OK(hipGetLastError());
-                HIP_OK(hipMemcpyAsync(&survivors, sc.counters + thin::kSurvivors, sizeof survivors, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipMemcpyAsync(&survivors, counters + thin::kSurvivors, sizeof survivors, hipMemcpyDeviceToHost, st));
                 HIP_OK(hipStreamSynchronize(st));
                 if (survivors >= undecided)  // (the lowest-key undecided point is always decided: this bounds the loop)
                     return fail(GIPUMA_HIP_ERR_DEVICE, "thin: round %u decided none of its %u undecided points", rounds, undecided);
                 undecided = survivors;
             }
-            HIP_OK(hipMemcpyAsync(&kept, sc.counters + thin::kKept, sizeof kept, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(&kept, counters + thin::kKept, sizeof kept, hipMemcpyDeviceToHost, st));
         }
         HIP_OK(hipEventRecord(sc.e[1], st));
         HIP_OK(hipStreamSynchronize(st));

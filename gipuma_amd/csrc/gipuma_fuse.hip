@@ -182,29 +182,6 @@ struct gipuma_hip_fusion {
 
 namespace {
 
-// the call's scratch: freed on every way out of gipuma_hip_fuse
-struct Scratch {
-    fuse::View *views = nullptr;
-    float4 *stage = nullptr;
-    uint8_t *flags = nullptr;
-    uint32_t *counts = nullptr, *offsets = nullptr, *total = nullptr;
-    hipStream_t st = nullptr, own = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Scratch()
-    {
-        if (st) (void)hipStreamSynchronize(st);  // (nothing of this call is in flight when its buffers go)
-        (void)hipFree(views);
-        (void)hipFree(stage);
-        (void)hipFree(flags);
-        (void)hipFree(counts);
-        (void)hipFree(offsets);
-        (void)hipFree(total);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (own) (void)hipStreamDestroy(own);
-    }
-};
-
 int run(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion *f)
 {
     const int V = d->n_views, npix = d->rows * d->cols;
@@ -215,13 +192,8 @@ int run(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion *f)
     f->n_views = V;
     f->per_view.assign(V, 0);
     HIP_OK(hipSetDevice(d->device_id));
-    Scratch sc;
-    if (d->stream) {
-        sc.st = (hipStream_t)d->stream;
-    } else {
-        HIP_OK(hipStreamCreateWithFlags(&sc.own, hipStreamNonBlocking));
-        sc.st = sc.own;
-    }
+    pm_host::CallScope sc;  // the call's scratch: freed on every way out of gipuma_hip_fuse
+    if (const int rc = sc.open(d->stream, 2)) return rc;
     hipStream_t st = sc.st;
     std::vector<fuse::View> table(V);
     for (int v = 0; v < V; ++v) {
@@ -245,29 +217,27 @@ int run(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion *f)
     p.depth_min = d->depth_min;
     p.depth_max = d->depth_max;
 
-    HIP_OK(hipMalloc(&sc.views, sizeof(fuse::View) * V));
-    HIP_OK(hipMalloc(&sc.stage, sizeof(float4) * 2 * (size_t)npix));
-    HIP_OK(hipMalloc(&sc.flags, (size_t)npix));
-    HIP_OK(hipMalloc(&sc.counts, sizeof(uint32_t) * nblocks));
-    HIP_OK(hipMalloc(&sc.offsets, sizeof(uint32_t) * nblocks));
-    HIP_OK(hipMalloc(&sc.total, sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&f->used, (size_t)V * npix));
+    fuse::View *views;
+    float4 *stage;
+    uint8_t *flags;
+    uint32_t *counts, *offsets, *total;
+    if (sc.alloc(views, V) || sc.alloc(stage, 2 * (size_t)npix) || sc.alloc(flags, npix) || sc.alloc(counts, nblocks) ||
+        sc.alloc(offsets, nblocks) || sc.alloc(total, 1))
+        return GIPUMA_HIP_ERR_DEVICE;
+    HIP_OK(hipMalloc(&f->used, (size_t)V * npix));  // (what outlives the call is the handle's)
     int64_t capacity = npix;
     HIP_OK(hipMalloc(&f->points, sizeof(float4) * 2 * (size_t)capacity));
-    HIP_OK(hipEventCreate(&sc.e0));
-    HIP_OK(hipEventCreate(&sc.e1));
-    HIP_OK(hipMemcpyAsync(sc.views, table.data(), sizeof(fuse::View) * V, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(views, table.data(), sizeof(fuse::View) * V, hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(f->used, 0, (size_t)V * npix, st));
 
-    HIP_OK(hipEventRecord(sc.e0, st));
+    HIP_OK(hipEventRecord(sc.e[0], st));
     for (int i = 0; i < V; ++i) {
-        hipLaunchKernelGGL(fuse::evaluate_kernel, dim3(nblocks), dim3(fuse::kBlock), 0, st, sc.views, p, i, f->used, sc.stage,
-                           sc.flags, sc.counts);
+        hipLaunchKernelGGL(fuse::evaluate_kernel, dim3(nblocks), dim3(fuse::kBlock), 0, st, views, p, i, f->used, stage, flags, counts);
         HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(fuse::scan_kernel, dim3(1), dim3(fuse::kScan), 0, st, sc.counts, sc.offsets, nblocks, sc.total);
+        hipLaunchKernelGGL(fuse::scan_kernel, dim3(1), dim3(fuse::kScan), 0, st, counts, offsets, nblocks, total);
         HIP_OK(hipGetLastError());
         uint32_t n = 0;
-        HIP_OK(hipMemcpyAsync(&n, sc.total, sizeof n, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(&n, total, sizeof n, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         if (n > (uint32_t)npix) return fail(GIPUMA_HIP_ERR_DEVICE, "fusion: a view emitted more points than it has pixels");
         if (f->n_points + n > capacity) {  // grow (doubling), keeping the points of the earlier views
@@ -286,16 +256,16 @@ int run(const gipuma_hip_fusion_desc *d, gipuma_hip_fusion *f)
             capacity = want;
         }
         if (n) {
-            hipLaunchKernelGGL(fuse::scatter_kernel, dim3(nblocks), dim3(fuse::kBlock), 0, st, sc.flags, sc.stage, sc.offsets, npix,
+            hipLaunchKernelGGL(fuse::scatter_kernel, dim3(nblocks), dim3(fuse::kBlock), 0, st, flags, stage, offsets, npix,
                                f->points + 2 * f->n_points);
             HIP_OK(hipGetLastError());
         }
         f->per_view[i] = n;
         f->n_points += n;
     }
-    HIP_OK(hipEventRecord(sc.e1, st));
+    HIP_OK(hipEventRecord(sc.e[1], st));
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipEventElapsedTime(&f->ms, sc.e0, sc.e1));
+    HIP_OK(hipEventElapsedTime(&f->ms, sc.e[0], sc.e[1]));
     return 0;
 }
 

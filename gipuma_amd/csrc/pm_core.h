@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pm_hash.h"
+
 // PM_APPROX = 1 builds the TOLERANCE-JUDGED flavour of every kernel (GIPUMA_HIP_FLAG_FAST, gipuma_hip_fast.hip): the
 // same algorithm, schedule, memory layout and random numbers, with the numerical model of rounds 1-5 (pm_sample.h,
 // PM_MODEL 0: x * (1/z) for x / z, fused multiply-adds in the sample loop) and arithmetic shortcuts of the kind the
@@ -140,16 +142,7 @@ struct Problem {  // lives in device memory, read through scalar loads (wave-uni
 // ---------------------------------------------------------------------------------------------
 // M4: counter-based uniform in (0,1] (stands in for curand_uniform, gipuma.cu:138-141)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t mix32(uint32_t h)
-{
-    h ^= h >> 16;
-    h *= 0x7feb352dU;
-    h ^= h >> 15;
-    h *= 0x846ca68bU;
-    h ^= h >> 16;
-    return h;
-}
-// the (seed, phase, y, x) prefix is hashed once per pixel, the draw index per number
+// the (seed, phase, y, x) prefix is hashed once per pixel, the draw index per number (mix32: pm_hash.h)
 __device__ __forceinline__ uint32_t rng_prefix(uint32_t seed, uint32_t phase, uint32_t x, uint32_t y)
 {
     uint32_t h = mix32(seed + 0x9E3779B9U);

@@ -5,12 +5,12 @@ import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from gipuma_amd import abi, synth
+from tests.abi_layout import assert_mirrors_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gipuma_hip.h")
@@ -43,24 +43,8 @@ def test_ctypes_structs_match_the_header_layout():
     }
     py = {"gipuma_hip_camera": abi.Camera, "gipuma_hip_params": abi.Params,
           "gipuma_hip_desc": abi.Desc, "gipuma_hip_timing": abi.Timing}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % HEADER, 'int main(void){']
     for s, fs in fields.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (s, s))
-        for f in fs:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (s, f, s, f))
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "l.c")
-        open(src, "w").write("\n".join(lines))
-        exe = os.path.join(td, "l")
-        subprocess.check_call(["gcc", "-o", exe, src])
-        out = subprocess.check_output([exe]).decode().split("\n")
-    got = dict(l.split() for l in out if l)
-    for s, fs in fields.items():
-        assert int(got[s]) == C.sizeof(py[s]), s
-        assert [f for f, _ in py[s]._fields_] == fs
-        for f in fs:
-            assert int(got["%s.%s" % (s, f)]) == getattr(py[s], f).offset, (s, f)
+        assert_mirrors_header(py[s], s, fs)
 
 
 def test_create_validates_the_descriptor():

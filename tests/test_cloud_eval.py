@@ -10,6 +10,7 @@ import pytest
 
 from gipuma_amd import abi
 from tests import cloud_ref
+from tests.abi_layout import assert_mirrors_header
 
 f32 = np.float32
 GRIDS = (0, 1, 2, 7, 256)  # 256 on a small cloud filling a cube: 2^24 cells, the scan's carry over 1024 chunks
@@ -302,21 +303,7 @@ def test_arguments_are_checked_before_the_device():
 
 
 def test_the_descriptor_mirrors_the_header():
-    import os
-    import subprocess
-    import tempfile
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gipuma_hip.h")
-    fields = [f for f, _ in abi.CloudDesc._fields_]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % header, 'int main(void){',
-             'printf("size %zu\\n", sizeof(gipuma_hip_cloud_desc));']
-    lines += ['printf("%s %%zu\\n", offsetof(gipuma_hip_cloud_desc, %s));' % (f, f) for f in fields] + ['return 0;}']
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "l.c"), "w").write("\n".join(lines))
-        subprocess.check_call(["gcc", "-o", os.path.join(td, "l"), os.path.join(td, "l.c")])
-        got = dict(l.split() for l in subprocess.check_output([os.path.join(td, "l")]).decode().split("\n") if l)
-    assert int(got["size"]) == C.sizeof(abi.CloudDesc)
-    for f in fields:
-        assert int(got[f]) == getattr(abi.CloudDesc, f).offset, f
+    assert_mirrors_header(abi.CloudDesc, "gipuma_hip_cloud_desc")
 
 
 def test_the_kernels_use_global_not_flat_memory_instructions_and_no_float_atomics():

@@ -13,6 +13,7 @@ import pytest
 
 from gipuma_amd import abi, cloud_eval
 from tests import thin_ref
+from tests.abi_layout import assert_mirrors_header
 
 f32 = np.float32
 GRIDS = (0, 1, 2, 7, 256)
@@ -299,21 +300,7 @@ def test_arguments_are_checked_before_the_device():
 
 
 def test_the_descriptor_mirrors_the_header():
-    import os
-    import subprocess
-    import tempfile
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "gipuma_hip.h")
-    fields = [f for f, _ in abi.ThinDesc._fields_]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % header, 'int main(void){',
-             'printf("size %zu\\n", sizeof(gipuma_hip_thin_desc));']
-    lines += ['printf("%s %%zu\\n", offsetof(gipuma_hip_thin_desc, %s));' % (f, f) for f in fields] + ['return 0;}']
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "l.c"), "w").write("\n".join(lines))
-        subprocess.check_call(["gcc", "-o", os.path.join(td, "l"), os.path.join(td, "l.c")])
-        got = dict(l.split() for l in subprocess.check_output([os.path.join(td, "l")]).decode().split("\n") if l)
-    assert int(got["size"]) == C.sizeof(abi.ThinDesc)
-    for f in fields:
-        assert int(got[f]) == getattr(abi.ThinDesc, f).offset, f
+    assert_mirrors_header(abi.ThinDesc, "gipuma_hip_thin_desc")
     assert "gipuma_hip_cloud_thin" in [s[0] for s in abi.SYMBOLS]
 
 

@@ -17,6 +17,7 @@ import torch
 
 from gipuma_amd import abi, cameras, dmb, fusion, synth
 from tests import fusion_ref
+from tests.abi_layout import assert_mirrors_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -290,22 +291,8 @@ def test_fusion_structs_match_the_header_layout():
               "gipuma_hip_fusion_desc": (abi.FusionDesc, ["abi_version", "rows", "cols", "n_views", "views", "disp_thresh",
                                                           "normal_thresh", "num_consistent", "depth_min", "depth_max",
                                                           "device_id", "stream"])}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % os.path.join(ROOT, "include", "gipuma_hip.h"),
-             'int main(void){']
-    for s, (_, fs) in fields.items():
-        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (s, s))
-        for f in fs:
-            lines.append('printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (s, f, s, f))
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "l.c")
-        open(src, "w").write("\n".join(lines))
-        subprocess.check_call(["gcc", "-o", os.path.join(td, "l"), src])
-        got = dict(l.split() for l in subprocess.check_output([os.path.join(td, "l")]).decode().split("\n") if l)
     for s, (py, fs) in fields.items():
-        assert int(got[s]) == C.sizeof(py) and [f for f, _ in py._fields_] == fs
-        for f in fs:
-            assert int(got["%s.%s" % (s, f)]) == getattr(py, f).offset, (s, f)
+        assert_mirrors_header(py, s, fs)
 
 
 def test_fusion_kernels_use_global_not_flat_memory_instructions():

@@ -17,6 +17,7 @@ import pytest
 from gipuma_amd import abi, batch, cameras, dmb, fusion, prior, synth
 from gipuma_amd.problem import GlobalState, Session, runcuda
 from tests import prior_ref, pyramid_ref
+from tests.abi_layout import assert_mirrors_header
 from tests.oracle_lib import OracleState
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -200,19 +201,7 @@ def test_prior_from_views_validates_its_arguments_and_needs_a_device():
 def test_prior_struct_matches_the_header_layout():
     fs = ["abi_version", "rows", "cols", "target", "n_sources", "sources", "costs", "max_cost", "depth_min", "depth_max",
           "grazing_cos", "fill", "device_id", "stream"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "%s"' % os.path.join(ROOT, "include", "gipuma_hip.h"),
-             'int main(void){', 'printf("size %zu\\n", sizeof(gipuma_hip_prior_desc));']
-    for f in fs:
-        lines.append('printf("%s %%zu\\n", offsetof(gipuma_hip_prior_desc, %s));' % (f, f))
-    lines.append('return 0;}')
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "l.c")
-        open(src, "w").write("\n".join(lines))
-        subprocess.check_call(["gcc", "-o", os.path.join(td, "l"), src])
-        got = dict(l.split() for l in subprocess.check_output([os.path.join(td, "l")]).decode().split("\n") if l)
-    assert int(got["size"]) == C.sizeof(abi.PriorDesc) and [f for f, _ in abi.PriorDesc._fields_] == fs
-    for f in fs:
-        assert int(got[f]) == getattr(abi.PriorDesc, f).offset, f
+    assert_mirrors_header(abi.PriorDesc, "gipuma_hip_prior_desc", fs)
 
 
 def test_prior_kernels_use_global_memory_instructions_one_64_bit_minimum_and_no_scratch():

@@ -15,7 +15,7 @@ Result = collections.namedtuple("Result", "keep kept dropped not_finite rounds u
 
 
 def mix32(h):
-    """mix32 of gipuma_amd/csrc/pm_core.h on a uint32 array, with uint32 wrap-around"""
+    """mix32 of gipuma_amd/csrc/pm_hash.h on a uint32 array, with uint32 wrap-around"""
     h = np.asarray(h, dtype=u32).copy()
     with np.errstate(over="ignore"):
         h ^= h >> u32(16)
