@@ -4,7 +4,8 @@
 // The contract (include/gipuma_hip.h) is restated on the CPU in numpy float32 by tests/cloud_ref.py as a
 // brute-force search.  For query a and target b, float32 without contraction (-ffp-contract=off):
 //     dx = a.x - b.x;  dy = a.y - b.y;  dz = a.z - b.z;  d2 = (dx*dx + dy*dy) + dz*dz
-//     b is a candidate iff it is finite and d2 <= r2 (r2 = max_dist * max_dist);  the answer is the smallest (d2, j).
+//     b is a candidate iff it is finite, d2 is finite and d2 <= r2 (r2 = max_dist * max_dist);  the answer is the
+//     smallest (d2, j).
 // A minimum over (d2, j) pairs does not depend on the order the candidates are visited in, so a uniform grid over the
 // targets may prune the search as long as it never skips a target the brute force would accept or prefer: the result
 // then equals the brute force in every bit.  Why each shortcut keeps that promise is written where it is taken
@@ -249,8 +250,10 @@ __device__ __forceinline__ void visit(const Rec *__restrict__ sorted, uint32_t b
         const Rec b = sorted[p];
         const float dx = ax - b.x, dy = ay - b.y, dz = az - b.z;
         const float d2 = (dx * dx + dy * dy) + dz * dz;
-        // (bj = -1 compares as the largest index)
-        if (d2 <= r2 && (d2 < best || (d2 == best && (uint32_t)b.j < (uint32_t)bj))) {
+        // A d2 of +inf (an overflow; r2 may be +inf too) is no candidate: +inf means "none" and nothing else.  It never
+        // passes d2 < best, and it ties best only while best is still INFINITY, i.e. bj = -1, which no index is below
+        // (a SIGNED comparison).  A finite best has bj >= 0: the lowest index wins the tie.
+        if (d2 <= r2 && (d2 < best || (d2 == best && b.j < bj))) {
             best = d2;
             bj = b.j;
         }

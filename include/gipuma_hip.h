@@ -373,9 +373,11 @@ int gipuma_hip_prior_from_views(const gipuma_hip_prior_desc *desc, float *prior_
  * For every query a_i (n_queries packed float32 xyz) the nearest target b_j (n_targets packed xyz) within max_dist.
  * Float32 without contraction, r2 = max_dist * max_dist:
  *     dx = a_i.x - b_j.x;  dy = a_i.y - b_j.y;  dz = a_i.z - b_j.z;  d2 = (dx*dx + dy*dy) + dz*dz
- *     j is a candidate  iff  b_j is finite in all three coordinates  and  d2 <= r2   (the radius is inclusive)
+ *     j is a candidate  iff  b_j is finite in all three coordinates  and  d2 is finite  and  d2 <= r2   (the radius is
+ *                            inclusive)
  *     d2_dev[i]  = the minimum of d2 over the candidates;  idx_dev[i] = the lowest j that attains it
  *     no candidate, or a_i not finite:  d2_dev[i] = +inf,  idx_dev[i] = -1
+ * +inf means "none" and nothing else: a d2 that overflows is no candidate even where r2 = +inf (max_dist above 1.8e19).
  * A minimum and a lowest index do not depend on the order of the candidates: the result is defined without reference
  * to the uniform grid the kernels search with, and it equals a brute-force search in every bit (tests/cloud_ref.py).
  * The grid -- one cell edge on all axes, `grid` cells along the longest axis of the finite targets' bounding box --
