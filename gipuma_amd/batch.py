@@ -34,7 +34,10 @@ MI355X-first differences from the shell loop:
   * --eval_cloud gt.ply (with --fuse): the fused cloud is scored against that reference cloud on the GPU -- accuracy,
     completeness, precision / recall / F-score within --eval_max_dist (gipuma_amd.cloud_eval) -- and the
     score joins the report as `cloud_score`.  --eval_reduce 0.2 thins the fused cloud to that minimum point spacing
-    first, as DTU's evaluation does.
+    first, as DTU's evaluation does (DESIGN.md 15);
+  * --fuse_neighbour_radius r --fuse_min_neighbours N (with --fuse): the fused cloud loses its isolated points -- those
+    with fewer than N other points within r (gipuma_amd.cloud_eval.drop_isolated) -- before fused.ply is
+    written and before --eval_cloud scores it.
 
 Images: what the reference's scripts hand to imread (main.cpp:739-751) -- PNG, JPG (through PIL), binary PGM / PPM.
 Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
@@ -323,10 +326,15 @@ def parse_args(argv):
     pa.add_argument("--eval_reduce", type=float, default=0.0,
                     help="with --eval_cloud: thin the fused cloud to this minimum point spacing before it is scored "
                          "(0: off; DTU uses 0.2; DESIGN.md 15)")
+    pa.add_argument("--fuse_neighbour_radius", type=float, default=0.0,
+                    help="with --fuse and --fuse_min_neighbours: drop the fused points that have fewer than that many other "
+                         "points within this radius, before fused.ply is written and scored (0: off; DESIGN.md 16)")
+    pa.add_argument("--fuse_min_neighbours", type=int, default=None,
+                    help="with --fuse_neighbour_radius: the count a fused point needs to stay")
     args = pa.parse_args(argv)
     # the reference parses these with sscanf("%f") into float fields (main.cpp:300-360)
     for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
-              "normal_thresh", "eval_max_dist", "eval_reduce"):
+              "normal_thresh", "eval_max_dist", "eval_reduce", "fuse_neighbour_radius"):
         setattr(args, k, float(np.float32(getattr(args, k))))
     if args.eval_cloud is not None and not args.fuse:
         pa.error("--eval_cloud scores the fused cloud: it needs --fuse")
@@ -336,6 +344,15 @@ def parse_args(argv):
         pa.error("--eval_reduce must be >= 0 and finite (0: off)")
     if args.eval_reduce > 0 and args.eval_cloud is None:
         pa.error("--eval_reduce thins the cloud that --eval_cloud scores: it needs --eval_cloud")
+    if not (args.fuse_neighbour_radius >= 0 and np.isfinite(args.fuse_neighbour_radius)):
+        pa.error("--fuse_neighbour_radius must be >= 0 and finite (0: off)")
+    if (args.fuse_neighbour_radius > 0) != (args.fuse_min_neighbours is not None):
+        pa.error("--fuse_neighbour_radius and --fuse_min_neighbours need each other")
+    if args.fuse_min_neighbours is not None and not 0 <= args.fuse_min_neighbours < 2 ** 31:
+        pa.error("--fuse_min_neighbours must be 0 .. 2^31 - 1")
+    if args.fuse_neighbour_radius > 0 and not args.fuse:
+        pa.error("--fuse_neighbour_radius filters the fused cloud: it needs --fuse")
+    args.fuse_min_neighbours = args.fuse_min_neighbours or 0
     if args.levels < 1:
         raise SystemExit("--levels must be >= 1")
     args.level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
@@ -370,10 +387,17 @@ def fuse_solved(scan):
                                [scan.P_all[names.index(n)] for n in fused_views], args.cam_scale, args.disp_thresh,
                                args.normal_thresh, args.num_consistent, args.depth_min, args.depth_max,
                                device_id=scan.dev[0].device.index, return_info=True)
+    filtered = {}
+    if args.fuse_neighbour_radius > 0:  # (the isolated points go before the cloud is written and scored)
+        from . import cloud_eval
+        kept, ms, _ = cloud_eval.drop_isolated(np.stack([points["x"], points["y"], points["z"]], axis=-1), args.fuse_neighbour_radius,
+                                               args.fuse_min_neighbours, device_id=scan.dev[0].device.index, return_info=True)
+        filtered = {"points_before_filter": int(len(points)), "filter_device_ms": ms}
+        points = points[kept]
     dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
     scan.fused_xyz = np.stack([points["x"], points["y"], points["z"]], axis=-1)  # (for --eval_cloud)
     return {"points": int(len(points)), "device_ms": info["device_ms"],
-            "views": [{"name": n, "emitted": int(c)} for n, c in zip(fused_views, info["per_view"])]}
+            "views": [{"name": n, "emitted": int(c)} for n, c in zip(fused_views, info["per_view"])], **filtered}
 
 
 def score_fused(scan):

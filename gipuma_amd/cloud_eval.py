@@ -1,8 +1,9 @@
 """Score a point cloud against a reference cloud on the GPU: accuracy and completeness, after thinning
-the cloud to a minimum point spacing when asked to.
+the cloud to a minimum point spacing and dropping its isolated points when asked to.
 
     python -m gipuma_amd.cloud_eval --cloud fused.ply --reference gt.ply --max_dist 20 --thresholds 0.5,1,2 \\
-        [--reduce 0.2 [--reduce_reference] [--seed N]] [--output report.json]
+        [--reduce 0.2 [--reduce_reference] [--seed N]] [--neighbour_radius 1 --min_neighbours 8] \\
+        [--write_cloud scored.ply] [--output report.json]
 
 DTU -- the data set this project is calibrated on -- scores a reconstruction cloud against cloud: accuracy is the distance
 from each reconstructed point to the nearest reference point, completeness the same the other way round, distances beyond
@@ -11,8 +12,11 @@ gipuma_amd/csrc/gipuma_cloud.hip: gfx950 kernels over a uniform grid, equal to a
 is no CPU fallback.  The means of the score are means over points, so they are weighted by how densely the fusion happened
 to sample each surface; DTU removes that by thinning the reconstruction to a minimum spacing first (its 0.2 mm resampling).
 --reduce does the same here (gipuma_hip_cloud_thin: points visited in a hashed order, a point kept unless a kept point lies
-within the spacing), and `thin` offers it for the delivered cloud.  Not part of the score here: DTU's observability masks
-and ground-plane removal.
+within the spacing), and `thin` offers it for the delivered cloud.  What a fused cloud still carries then are floaters:
+points, or small clumps of points, far from any surface.  --neighbour_radius / --min_neighbours drop every point with
+fewer than that many other points within the radius (gipuma_hip_cloud_neighbours; `drop_isolated`, `neighbour_counts`),
+after the thinning: a count means the same everywhere only once the density is normalised.  --write_cloud writes the cloud
+as it is scored.  Not part of the score here: DTU's observability masks and ground-plane removal.
 """
 import argparse
 import ctypes as C
@@ -27,6 +31,7 @@ THRESHOLDS = (0.5, 1.0, 2.0)
 _STATS = ("grid", "cells_x", "cells_y", "cells_z", "early_out", "searched")
 ORDERS = {"hashed": 0, "index": 1}
 _THIN_INFO = ("kept", "dropped", "not_finite", "rounds", "grid", "cells_x", "cells_y", "cells_z")
+_NEIGHBOUR_INFO = ("kept", "dropped", "not_finite", "saturated", "grid", "cells_x", "cells_y", "cells_z")
 
 
 def _device_cloud(a, device, keep):
@@ -103,6 +108,51 @@ def thin(points, radius, seed=0, order="hashed", grid=0, device_id=0, return_inf
     return (idx, ms, info) if return_info else idx
 
 
+def neighbours(points, radius, min_neighbours=0, max_count=0, grid=0, device_id=0, counts=True, keep=True):
+    """The contract of gipuma_hip_cloud_neighbours on the (n, 3) cloud `points` (a numpy array or a torch tensor; a device
+    tensor is passed by pointer): (count, keep, device_ms, info) -- count a torch int32 tensor on the device holding the
+    uint32 counts' bits, keep a torch uint8 tensor on the device, one entry per point each, or None where `counts` /
+    `keep` is False; info dict(kept, dropped, not_finite, saturated, grid, cells_x, cells_y, cells_z)."""
+    import torch
+    lib = abi.load_library()
+    if lib.gipuma_hip_device_count() < 1:
+        raise abi.GipumaHipError("counting a cloud's neighbours needs a HIP device; gipuma_amd has no CPU fallback")
+    dev, held = torch.device("cuda", device_id), []
+    d = abi.NeighboursDesc()
+    d.abi_version = abi.ABI_VERSION
+    d.points, d.n_points = _device_cloud(points, dev, held)
+    d.radius, d.min_neighbours, d.max_count, d.grid, d.device_id = float(radius), int(min_neighbours), int(max_count), int(grid), device_id
+    count_t = torch.empty(d.n_points, dtype=torch.int32, device=dev) if counts else None
+    keep_t = torch.empty(d.n_points, dtype=torch.uint8, device=dev) if keep else None
+    torch.cuda.synchronize(dev)  # (the library works on a stream of its own: the cloud must be complete)
+    info, ms = (C.c_int64 * len(_NEIGHBOUR_INFO))(), C.c_float()
+    abi.check(lib, lib.gipuma_hip_cloud_neighbours(C.byref(d), count_t.data_ptr() if counts and d.n_points else None,
+                                                   keep_t.data_ptr() if keep and d.n_points else None, info, C.byref(ms)),
+              "gipuma_hip_cloud_neighbours")
+    return count_t, keep_t, ms.value, {k: int(v) for k, v in zip(_NEIGHBOUR_INFO, info)}
+
+
+def neighbour_counts(points, radius, max_count=0, grid=0, device_id=0, return_info=False):
+    """For every point of the cloud the number of OTHER finite points within `radius` (inclusive; an exact copy counts;
+    DESIGN.md 16), 0 for a point that is not finite; with max_count > 0 the counts saturate there.  Returns uint32 counts
+    (numpy); with return_info also device_ms and dict(kept, dropped, not_finite, saturated, grid, cells_x, cells_y,
+    cells_z) -- min_neighbours is 0 here, so every finite point is `kept`."""
+    count, _, ms, info = neighbours(points, radius, 0, max_count, grid, device_id, keep=False)
+    out = count.cpu().numpy().view(np.uint32)
+    return (out, ms, info) if return_info else out
+
+
+def drop_isolated(points, radius, min_neighbours, grid=0, device_id=0, return_info=False):
+    """Drops the isolated points of a cloud: a point is kept iff it is finite and at least `min_neighbours`
+    other finite points lie within `radius` (inclusive).  Counting stops at max(min_neighbours, 1), so points in dense
+    regions stop early.  Returns the ascending int64 indices of the kept points (numpy), like `thin`; with return_info also
+    device_ms and dict(kept, dropped, not_finite, saturated, grid, cells_x, cells_y, cells_z)."""
+    import torch
+    _, keep, ms, info = neighbours(points, radius, min_neighbours, max(int(min_neighbours), 1), grid, device_id, counts=False)
+    idx = torch.nonzero(keep).reshape(-1).cpu().numpy().astype(np.int64)
+    return (idx, ms, info) if return_info else idx
+
+
 def direction_score(d2, thresholds):
     """One direction of the score from its squared distances (float32, +inf: none): ({mean, median, found, none} over the
     points that found a neighbour, [share of ALL points with d <= tau for tau in thresholds] -- "none" is a miss)."""
@@ -121,34 +171,51 @@ def combine(acc, prec, comp, rec, thresholds):
     return out
 
 
-def _reduced(a, radius, seed, device_id):
-    """the cloud `a` thinned to `radius` (thin, hashed order), as a device tensor, and (device_ms, rounds)"""
+def _taken(a, idx, device_id):
+    """the rows `idx` (numpy int64) of the cloud `a`, as a float32 device tensor"""
     import torch
-    idx, ms, info = thin(a, radius, seed=seed, device_id=device_id, return_info=True)
     dev = torch.device("cuda", device_id)
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-    return t.to(device=dev, dtype=torch.float32)[torch.from_numpy(idx).to(dev)], (ms, info["rounds"])
+    return t.to(device=dev, dtype=torch.float32)[torch.from_numpy(idx).to(dev)]
+
+
+def _reduced(a, radius, seed, device_id):
+    """the cloud `a` thinned to `radius` (thin, hashed order), as a device tensor, the kept indices and (device_ms, rounds)"""
+    idx, ms, info = thin(a, radius, seed=seed, device_id=device_id, return_info=True)
+    return _taken(a, idx, device_id), idx, (ms, info["rounds"])
 
 
 def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device_id=0, reduce=0.0, reduce_reference=False,
-          seed=0):
+          seed=0, neighbour_radius=0.0, min_neighbours=0, return_indices=False):
     """Both directions of the score.  accuracy: {mean, median, found, none} of d = sqrt(d2) (float64, on the host) over
     the cloud's points that found a reference point within max_dist; completeness: the same over the reference's points;
     precision / recall per threshold: the share of ALL cloud / reference points with d <= tau; fscore = 2PR / (P + R), 0
     when both are 0.  Empty clouds give NaN means and 0 counts.  Also the point counts, both device times and the grids.
     reduce > 0: the cloud is thinned to that spacing (thin, hashed order with `seed`) before both searches, with
     reduce_reference the reference too -- DTU thins the reconstruction only.  The report then also carries reduce,
-    cloud_points_before, reference_points_before, thin_rounds and thin_device_ms (cloud first, then the reference)."""
+    cloud_points_before, reference_points_before, thin_rounds and thin_device_ms (cloud first, then the reference).
+    neighbour_radius > 0: the cloud -- never the reference -- then loses its isolated points (drop_isolated with
+    min_neighbours), after the thinning and before both searches; the report then also carries neighbour_radius,
+    min_neighbours, cloud_points_before_filter and filter_device_ms.  return_indices: (report, the ascending indices into
+    `cloud` of the points scored, or None where all were)."""
     thresholds = [float(t) for t in thresholds]
     if not (reduce >= 0 and np.isfinite(reduce)):
         raise ValueError("reduce must be >= 0 and finite, got %r" % (reduce,))
-    before, thinned = (int(cloud.shape[0]), int(reference.shape[0])), []
+    if not (neighbour_radius >= 0 and np.isfinite(neighbour_radius)):
+        raise ValueError("neighbour_radius must be >= 0 and finite, got %r" % (neighbour_radius,))
+    if int(min_neighbours) != min_neighbours or min_neighbours < 0:
+        raise ValueError("min_neighbours must be an integer >= 0, got %r" % (min_neighbours,))
+    before, thinned, indices = (int(cloud.shape[0]), int(reference.shape[0])), [], None
     if reduce > 0:
-        cloud, t = _reduced(cloud, reduce, seed, device_id)
+        cloud, indices, t = _reduced(cloud, reduce, seed, device_id)
         thinned.append(t)
         if reduce_reference:
-            reference, t = _reduced(reference, reduce, seed, device_id)
+            reference, _, t = _reduced(reference, reduce, seed, device_id)
             thinned.append(t)
+    if neighbour_radius > 0:  # (after the thinning: a count means the same everywhere once the density is normalised)
+        before_filter = int(cloud.shape[0])
+        kept, filter_ms, _ = drop_isolated(cloud, neighbour_radius, min_neighbours, device_id=device_id, return_info=True)
+        cloud, indices = _taken(cloud, kept, device_id), kept if indices is None else indices[kept]
     a_d2, _, a_ms, a_info = nearest(cloud, reference, max_dist, grid, device_id, return_info=True)
     c_d2, _, c_ms, c_info = nearest(reference, cloud, max_dist, grid, device_id, return_info=True)
     out = combine(*direction_score(a_d2, thresholds), *direction_score(c_d2, thresholds), thresholds)
@@ -158,7 +225,10 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
     if reduce > 0:
         out.update({"reduce": float(reduce), "cloud_points_before": before[0], "reference_points_before": before[1],
                     "thin_rounds": [r for _, r in thinned], "thin_device_ms": [ms for ms, _ in thinned]})
-    return out
+    if neighbour_radius > 0:
+        out.update({"neighbour_radius": float(neighbour_radius), "min_neighbours": int(min_neighbours),
+                    "cloud_points_before_filter": before_filter, "filter_device_ms": filter_ms})
+    return (out, indices) if return_indices else out
 
 
 def parse_args(argv):
@@ -173,6 +243,13 @@ def parse_args(argv):
                     help="thin the cloud to this minimum point spacing before scoring (0: off; DTU uses 0.2)")
     pa.add_argument("--reduce_reference", action="store_true", help="with --reduce: thin the reference as well")
     pa.add_argument("--seed", type=int, default=0, help="with --reduce: seed of the order the points are visited in")
+    pa.add_argument("--neighbour_radius", type=float, default=0.0,
+                    help="with --min_neighbours: after --reduce, drop the cloud's points that have fewer than that many "
+                         "other points within this radius (0: off)")
+    pa.add_argument("--min_neighbours", type=int, default=None, help="with --neighbour_radius: the count a point needs to stay")
+    pa.add_argument("--write_cloud", default=None,
+                    help="write the cloud as it is scored, after --reduce and / or --neighbour_radius, as a binary PLY with "
+                         "every vertex property of --cloud")
     pa.add_argument("--device", type=int, default=0)
     pa.add_argument("--output", default=None, help="write the report (JSON) here")
     args = pa.parse_args(argv)
@@ -194,15 +271,27 @@ def parse_args(argv):
         pa.error("--reduce_reference needs --reduce")
     if not 0 <= args.seed < 2 ** 32:
         pa.error("--seed must be 0 .. 2^32 - 1")
+    args.neighbour_radius = float(np.float32(args.neighbour_radius))
+    if not (args.neighbour_radius >= 0 and np.isfinite(args.neighbour_radius)):
+        pa.error("--neighbour_radius must be >= 0 and finite (0: off)")
+    if (args.neighbour_radius > 0) != (args.min_neighbours is not None):
+        pa.error("--neighbour_radius and --min_neighbours need each other")
+    if args.min_neighbours is not None and not 0 <= args.min_neighbours < 2 ** 31:
+        pa.error("--min_neighbours must be 0 .. 2^31 - 1")
+    args.min_neighbours = args.min_neighbours or 0
     return args
 
 
 def main(argv=None):
     args = parse_args(argv)
-    report = score(dmb.read_ply_xyz(args.cloud), dmb.read_ply_xyz(args.reference), args.max_dist, args.thresholds,
-                   grid=args.grid, device_id=args.device, reduce=args.reduce, reduce_reference=args.reduce_reference,
-                   seed=args.seed)
+    vertices = dmb.read_ply_vertices(args.cloud) if args.write_cloud else None  # (refused before anything is computed)
+    report, indices = score(dmb.read_ply_xyz(args.cloud), dmb.read_ply_xyz(args.reference), args.max_dist, args.thresholds,
+                            grid=args.grid, device_id=args.device, reduce=args.reduce, reduce_reference=args.reduce_reference,
+                            seed=args.seed, neighbour_radius=args.neighbour_radius, min_neighbours=args.min_neighbours,
+                            return_indices=True)
     report.update({"cloud": args.cloud, "reference": args.reference})
+    if args.write_cloud:
+        dmb.write_ply_vertices(args.write_cloud, vertices if indices is None else vertices[indices])
     if args.output:
         with open(args.output, "w") as f:
             json.dump(report, f, indent=1)
@@ -214,9 +303,14 @@ def main(argv=None):
              "/".join("%g" % t for t in args.thresholds), report["accuracy_device_ms"], report["completeness_device_ms"]))
     if args.reduce > 0:
         print("thinned to a spacing of %g first: cloud %d -> %d points, reference %d -> %d, %s rounds, %s ms on device"
-              % (args.reduce, report["cloud_points_before"], report["cloud_points"], report["reference_points_before"],
+              % (args.reduce, report["cloud_points_before"], report.get("cloud_points_before_filter", report["cloud_points"]),
+                 report["reference_points_before"],
                  report["reference_points"], "/".join("%d" % r for r in report["thin_rounds"]),
                  "/".join("%.2f" % m for m in report["thin_device_ms"])))
+    if args.neighbour_radius > 0:
+        print("points with fewer than %d others within %g dropped: cloud %d -> %d points, %.2f ms on device"
+              % (args.min_neighbours, args.neighbour_radius, report["cloud_points_before_filter"], report["cloud_points"],
+                 report["filter_device_ms"]))
     return 0
 
 

@@ -534,6 +534,77 @@ inline int automatic_grid(float longest, float radius)
 
 }  // namespace thin
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Counting a point's neighbours within a radius, to drop the isolated ones (restated on the CPU by
+// tests/neighbours_ref.py).  The contract, defined without any grid: for a finite point i,
+//     exact(i) = #{ j != i : P_j finite and d2(i, j) <= r2 }      (cloud's d2, the thinning's inclusive radius; j != i by
+//                                                                  index, so an exact copy is a neighbour)
+//     count(i) = max_count > 0 ? min(exact(i), max_count) : exact(i);   keep(i) = count(i) >= min_neighbours
+// and 0, 0 for a point that is not finite, which no other point counts either.  A count is the cardinality of a set: it
+// does not depend on the order the records are visited in.
+//
+// Launches, all on one stream:
+//   cloud::box_*, count_kernel<false>, scan_kernel, scatter_kernel    the thinning's set-up, through the same host steps:
+//                                                  cloud::Box, cloud::lay_out (thin::automatic_grid), cloud::sort_by_cell<false>
+//   support::count_kernel, once                    one lane per sorted position over the thinning's cell range (thin::kReach:
+//                                                  its derivation is why no neighbour is skipped here either); the lane's
+//                                                  counter goes to the caller's index
+// The lanes of a wavefront are neighbours in the sorted order: they stand in the same or in adjacent cells, walk the same
+// rows and load the same records, which the vector cache serves once per wavefront.  There is no LDS staging.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace support {
+
+using cloud::cell_of;
+using cloud::Grid;
+using cloud::kBlock;
+using cloud::Rec;
+
+enum { kKept = cloud::kStats, kSaturated, kCounters };  // the device counters, behind cloud's (kTargets: the finite points)
+
+// *n_sorted: the number of sorted (finite) points, as the histogram left it on the device.  max_count = 0 counts without
+// a limit: a counter never comes back to 0 (fewer than 2^31 points).  With a limit the lane leaves all three loops when
+// it reaches it; min_neighbours <= max_count then, so stopping there cannot change `kept`.
+__global__ __launch_bounds__(kBlock) void count_kernel(const Rec *__restrict__ sorted, const uint32_t *__restrict__ ends,
+                                                       const uint32_t *__restrict__ n_sorted, Grid g, float reach, uint32_t max_count,
+                                                       uint32_t min_neighbours, uint32_t *__restrict__ count_out,
+                                                       uint8_t *__restrict__ keep_out, uint32_t *__restrict__ counters)
+{
+    const uint32_t pos = blockIdx.x * kBlock + threadIdx.x;
+    bool kept = false, full = false;
+    if (pos < *n_sorted) {
+        const Rec a = sorted[pos];
+        const int x0 = cell_of(a.x - reach, g.lo[0], g.inv_h, g.g[0]), x1 = cell_of(a.x + reach, g.lo[0], g.inv_h, g.g[0]);
+        const int y0 = cell_of(a.y - reach, g.lo[1], g.inv_h, g.g[1]), y1 = cell_of(a.y + reach, g.lo[1], g.inv_h, g.g[1]);
+        const int z0 = cell_of(a.z - reach, g.lo[2], g.inv_h, g.g[2]), z1 = cell_of(a.z + reach, g.lo[2], g.inv_h, g.g[2]);
+        uint32_t count = 0;
+        for (int z = z0; z <= z1 && !full; ++z)
+            for (int y = y0; y <= y1 && !full; ++y) {
+                const int c0 = (z * g.g[1] + y) * g.g[0] + x0, c1 = c0 + (x1 - x0);
+                const uint32_t end = ends[c1];
+                for (uint32_t p = c0 ? ends[c0 - 1] : 0u; p < end; ++p) {
+                    const Rec b = sorted[p];
+                    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 <= g.r2 && p != pos && ++count == max_count) {
+                        full = true;
+                        break;
+                    }
+                }
+            }
+        kept = count >= min_neighbours;
+        if (count_out) count_out[a.j] = count;
+        if (keep_out && kept) keep_out[a.j] = 1;  // (both outputs come in cleared)
+    }
+    // the counters: one atomic each per wavefront (integer sums: the totals do not depend on the order)
+    const uint64_t bk = __ballot(kept), bf = __ballot(full);
+    if ((threadIdx.x & 63) == 0) {
+        if (bk) atomicAdd(&counters[kKept], (uint32_t)__popcll(bk));
+        if (bf) atomicAdd(&counters[kSaturated], (uint32_t)__popcll(bf));
+    }
+}
+
+}  // namespace support
+
 namespace {
 
 thread_local int64_t last_stats[6] = {0, 0, 0, 0, 0, 0};  // gipuma_hip_cloud_last_stats
@@ -682,6 +753,61 @@ int run_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int64_t info[8], 
     return 0;
 }
 
+int run_neighbours(const gipuma_hip_neighbours_desc *d, uint32_t *count_dev, uint8_t *keep_dev, int64_t info[8], float *device_ms)
+{
+    const uint32_t n = (uint32_t)d->n_points;
+    HIP_OK(hipSetDevice(d->device_id));
+    pm_host::CallScope sc;
+    if (const int rc = sc.open(d->stream, 2)) return rc;
+    hipStream_t st = sc.st;
+    int64_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kept, dropped, not finite, saturated, G, cells x, y, z
+    float ms = 0.f;
+
+    if (n) {
+        // both outputs come out of the kernel with the finite points' entries written; the box of the finite points
+        cloud::Box box;
+        if (const int rc = box.alloc(sc, n)) return rc;
+        HIP_OK(hipEventRecord(sc.e[0], st));
+        if (count_dev) HIP_OK(hipMemsetAsync(count_dev, 0, sizeof(uint32_t) * n, st));
+        if (keep_dev) HIP_OK(hipMemsetAsync(keep_dev, 0, n, st));
+        if (const int rc = box.enqueue(st, d->points, n)) return rc;
+        if (const int rc = box.read(st)) return rc;
+
+        uint32_t counters[support::kCounters] = {};
+        if (box.any_finite()) {  // (else: nothing is counted, nothing kept)
+            // the thinning's grid, on the thinning's condition: thin::kReach is derived for a radius in 2^-40 .. 2^40
+            const cloud::Layout l = cloud::lay_out(box, d->grid ? d->grid : thin::automatic_grid(box.longest_extent(), d->radius),
+                                                   d->radius * d->radius, d->radius >= 0x1p-40f && d->radius <= 0x1p40f);
+            memcpy(out + 4, l.report, sizeof l.report);
+
+            uint32_t *cells, *counters_dev;
+            int32_t *cellid;
+            cloud::Rec *sorted;
+            if (sc.alloc(cells, l.ncells) || sc.alloc(counters_dev, support::kCounters) || sc.alloc(cellid, n) || sc.alloc(sorted, n))
+                return GIPUMA_HIP_ERR_DEVICE;
+            HIP_OK(hipMemsetAsync(cells, 0, sizeof(uint32_t) * l.ncells, st));
+            HIP_OK(hipMemsetAsync(counters_dev, 0, sizeof counters, st));
+            if (const int rc = cloud::sort_by_cell<false>(st, d->points, n, l, cellid, cells, sorted, nullptr, nullptr, counters_dev, nullptr))
+                return rc;
+            hipLaunchKernelGGL(support::count_kernel, cloud::blocks_for(n), dim3(cloud::kBlock), 0, st, sorted, cells,
+                               counters_dev + cloud::kTargets, l.g, thin::kReach * d->radius, (uint32_t)d->max_count,
+                               (uint32_t)d->min_neighbours, count_dev, keep_dev, counters_dev);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipMemcpyAsync(counters, counters_dev, sizeof counters, hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipEventRecord(sc.e[1], st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(&ms, sc.e[0], sc.e[1]));
+        out[0] = counters[support::kKept];
+        out[1] = (int64_t)counters[cloud::kTargets] - counters[support::kKept];
+        out[2] = (int64_t)n - counters[cloud::kTargets];
+        out[3] = counters[support::kSaturated];
+    }
+    if (info) memcpy(info, out, sizeof out);
+    if (device_ms) *device_ms = ms;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -721,6 +847,25 @@ int gipuma_hip_cloud_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int6
     if (d->grid < 0 || d->grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "thin: grid must be 0 (automatic) or 1..256");
     if (const int rc = pm_host::check_device(d->device_id)) return rc;
     return run_thin(d, keep_dev, info, device_ms);
+}
+
+int gipuma_hip_cloud_neighbours(const gipuma_hip_neighbours_desc *d, uint32_t *count_dev, uint8_t *keep_dev, int64_t info[8],
+                                float *device_ms)
+{
+    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
+    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: abi_version mismatch");
+    if (d->n_points < 0) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: negative point count");
+    if (d->n_points >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "neighbours: a cloud may hold at most 2^31 - 1 points");
+    if (d->n_points && (!d->points || (!count_dev && !keep_dev)))
+        return fail(GIPUMA_HIP_ERR_ARG, "neighbours: null pointer with a non-zero point count");
+    if (!(d->radius > 0.f) || !std::isfinite(d->radius)) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: radius must be > 0 and finite");
+    if (d->min_neighbours < 0) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: min_neighbours must be >= 0");
+    if (d->max_count < 0) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: max_count must be >= 0 (0: exact counts)");
+    if (d->max_count > 0 && d->min_neighbours > d->max_count)
+        return fail(GIPUMA_HIP_ERR_ARG, "neighbours: min_neighbours must not exceed a max_count > 0");
+    if (d->grid < 0 || d->grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: grid must be 0 (automatic) or 1..256");
+    if (const int rc = pm_host::check_device(d->device_id)) return rc;
+    return run_neighbours(d, count_dev, keep_dev, info, device_ms);
 }
 
 }  // extern "C"

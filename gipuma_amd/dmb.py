@@ -204,3 +204,68 @@ def read_ply_xyz(path):
             except (IndexError, ValueError):
                 raise ValueError("%s: vertex %d of %d is incomplete" % (path, r, n))
         return out
+
+
+_PLY_NAMES = {"i1": "char", "u1": "uchar", "i2": "short", "u2": "ushort", "i4": "int", "u4": "uint", "f4": "float", "f8": "double"}
+
+
+def read_ply_vertices(path):
+    """A PLY file's element `vertex` as a structured array, in file order: every property under its own name and declared
+    type (little-endian), so that a selection of the vertices can be written back with write_ply_vertices.  Reads what
+    read_ply_xyz reads -- binary_little_endian or ascii, other elements skipped -- and refuses what it refuses, a list
+    property in element vertex in either format included; also a property name that occurs twice."""
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        fmt, elements = _ply_header(f, path)
+        names = [e[0] for e in elements]
+        if "vertex" not in names:
+            raise ValueError("%s: no element vertex" % path)
+        k = names.index("vertex")
+        _, n, props = elements[k]
+        if any(isinstance(t, tuple) for _, t in props):
+            raise ValueError("%s: a list property in element vertex is not read here" % path)
+        if len({p for p, _ in props}) != len(props):
+            raise ValueError("%s: element vertex declares a property twice" % path)
+        dt = np.dtype([(p, "<" + t) for p, t in props])
+        if fmt == "binary_little_endian":
+            for _, cnt, pr in elements[:k]:
+                _ply_skip_binary(f, path, cnt, pr)
+            if f.tell() > size or n * dt.itemsize > size - f.tell():
+                raise ValueError("%s: the file cannot hold %d vertices of %d bytes" % (path, n, dt.itemsize))
+            return np.fromfile(f, dtype=dt, count=n)
+        for _, cnt, _ in elements[:k]:
+            for _ in range(cnt):
+                if not f.readline():
+                    raise ValueError("%s: file ends before element vertex" % path)
+        if n * 2 * len(props) > size - f.tell() + 1:  # (a one-digit number and its separator take 2 bytes)
+            raise ValueError("%s: the file cannot hold %d vertices" % (path, n))
+        out = np.empty(n, dtype=dt)
+        for r in range(n):
+            w = f.readline().split()
+            try:
+                if len(w) < len(props):
+                    raise IndexError
+                out[r] = tuple(float(v) if t[0] == "f" else int(v) for v, (_, t) in zip(w, props))
+            except (IndexError, ValueError, OverflowError):
+                raise ValueError("%s: vertex %d of %d is incomplete" % (path, r, n))
+        return out
+
+
+def write_ply_vertices(path, vertices):
+    """a structured array of scalar fields (read_ply_vertices' result, or rows of it) as a binary_little_endian PLY with
+    one element, `vertex`: every field a property of its name and type, in the array's order.  Written from this project's
+    own vertex layout, the file is byte for byte write_points_ply's."""
+    v = np.asarray(vertices)
+    if v.dtype.names is None or v.ndim != 1:
+        raise ValueError("write_ply_vertices takes a one-dimensional structured array")
+    kinds = [v.dtype[name].newbyteorder("<").str[1:] for name in v.dtype.names]
+    if any(k not in _PLY_NAMES for k in kinds):
+        raise ValueError("a vertex property must be one of PLY's scalar types, got %s" % (v.dtype,))
+    packed = np.empty(len(v), dtype=np.dtype([(name, "<" + k) for name, k in zip(v.dtype.names, kinds)]))
+    for name in v.dtype.names:
+        packed[name] = v[name]
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(packed)).encode())
+        f.write("".join("property %s %s\n" % (_PLY_NAMES[k], name) for name, k in zip(v.dtype.names, kinds)).encode())
+        f.write(b"end_header\n")
+        packed.tofile(f)

@@ -439,6 +439,41 @@ typedef struct gipuma_hip_thin_desc {
  * of the per-round survivor count included) may be NULL. */
 int gipuma_hip_cloud_thin(const gipuma_hip_thin_desc *desc, uint8_t *keep_dev, int64_t info[8], float *device_ms);
 
+/* ---- counting a point's neighbours within a radius: dropping the isolated points of a cloud ----
+ * P: n_points packed float32 xyz.  d2(i, j) and r2 = radius * radius are the thinning's, float32 without contraction;
+ * the neighbour relation is the thinning's radius graph, plain d2 <= r2, inclusive (inf <= inf holds where r2 = +inf).
+ *     P_i not finite in all three coordinates:  count(i) = 0, keep(i) = 0 -- never kept, never counted by another point
+ *     otherwise:  exact(i) = the number of j != i with P_j finite and d2(i, j) <= r2   (j != i by index: an exact copy
+ *                            of P_i is a neighbour)
+ *                 count(i) = max_count > 0 ? min(exact(i), max_count) : exact(i)
+ *                 keep(i)  = count(i) >= min_neighbours
+ * min_neighbours <= max_count is required where max_count > 0, so that saturation never changes keep; it lets a point in
+ * a dense region stop counting early.  A count is the cardinality of a set: it is defined without reference to the grid or
+ * to the order the kernel visits the points in, and equal to a brute force in every bit (tests/neighbours_ref.py); d2 is
+ * bitwise symmetric, so exact counts sum to an even number.  `grid` is the thinning's and changes the time only; 0 lets
+ * the library choose a cell edge of about the radius, at most 256 cells.
+ * n_points = 0 writes nothing.  Blocks until the outputs are complete; the cloud must be complete on desc->stream's
+ * terms when the call is made.  Scratch (about 20 bytes per point and 4 per cell) is allocated for the call and freed
+ * before it returns, on every error path too. */
+typedef struct gipuma_hip_neighbours_desc {
+    uint32_t abi_version;   /* GIPUMA_HIP_ABI_VERSION */
+    int64_t n_points;       /* < 2^31; more: GIPUMA_HIP_ERR_UNSUPPORTED */
+    const float *points;    /* device pointer, packed xyz float32 */
+    float radius;           /* > 0 and finite, else GIPUMA_HIP_ERR_ARG */
+    int32_t min_neighbours; /* >= 0 */
+    int32_t max_count;      /* 0: exact counts; > 0: counts saturate there, and min_neighbours <= max_count */
+    int32_t grid;           /* 0: automatic; 1..256: cells along the longest axis */
+    int32_t device_id;      /* HIP device ordinal */
+    void *stream;           /* hipStream_t to launch on, NULL = one the library creates for the call */
+} gipuma_hip_neighbours_desc;
+
+/* count_dev: n_points uint32, device; keep_dev: n_points bytes, device.  Either may be NULL, not both where n_points > 0
+ * (GIPUMA_HIP_ERR_ARG).  info (points kept, finite points dropped, points not finite, points whose count reached a
+ * max_count > 0, cells along the longest axis, cells along x, y and z) and device_ms (HIP events around everything the
+ * call enqueues) may be NULL. */
+int gipuma_hip_cloud_neighbours(const gipuma_hip_neighbours_desc *desc, uint32_t *count_dev, uint8_t *keep_dev,
+                                int64_t info[8], float *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
