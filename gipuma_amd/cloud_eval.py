@@ -42,59 +42,67 @@ def _device_cloud(a, device, keep):
     return (abi.device_plane(a, device, keep) if n else None), n
 
 
+def _open(what, desc_type, device_id):
+    """every call's prelude: (torch, lib, a `desc_type` with abi_version and device_id set, the torch device, the list that
+    keeps the device clouds handed over alive until the caller returns); `what` needs a HIP device, without one this raises"""
+    # (torch first: it brings a HIP runtime of its own, and a process that loaded the library's first cannot start torch's)
+    import torch
+    lib = abi.load_library()
+    if lib.gipuma_hip_device_count() < 1:
+        raise abi.GipumaHipError("%s needs a HIP device; gipuma_amd has no CPU fallback" % what)
+    return torch, lib, desc_type(abi_version=abi.ABI_VERSION, device_id=device_id), torch.device("cuda", device_id), []
+
+
+def _figures(names, values):
+    return {k: int(v) for k, v in zip(names, values)}
+
+
+def _call(torch, lib, name, d, dev, outs, names):
+    """lib.<name>(d, *addresses of `outs` (NULL for None or an empty tensor), int64 figures, device_ms): (figures dict, ms)"""
+    torch.cuda.synchronize(dev)  # (the library works on a stream of its own: the clouds must be complete)
+    figures, ms = (C.c_int64 * len(names))(), C.c_float()
+    abi.check(lib, getattr(lib, name)(C.byref(d), *[t.data_ptr() if t is not None and t.numel() else None for t in outs],
+                                      figures, C.byref(ms)), name)
+    return _figures(names, figures), ms.value
+
+
+def _indices(keep):
+    """the ascending int64 indices (numpy) of the points a device mask keeps"""
+    import torch
+    return torch.nonzero(keep).reshape(-1).cpu().numpy().astype(np.int64)
+
+
 def nearest(queries, targets, max_dist, grid=0, device_id=0, return_info=False):
     """For every query the nearest target within max_dist (the contract of gipuma_hip_cloud_nearest).  queries, targets:
     (n, 3) numpy arrays or torch tensors; device tensors are passed by pointer.  Returns (d2, idx, device_ms): float32
     squared distances (+inf: none), int32 target indices (-1: none), both numpy, and the device time in ms; with
     return_info also dict(found, none, grid, cells_x, cells_y, cells_z, early_out, searched)."""
-    # (torch first: it brings a HIP runtime of its own, and a process that loaded the library's first cannot start torch's)
-    import torch
-    lib = abi.load_library()
-    if lib.gipuma_hip_device_count() < 1:
-        raise abi.GipumaHipError("the cloud search needs a HIP device; gipuma_amd has no CPU fallback")
-    dev, keep = torch.device("cuda", device_id), []  # keep: the device clouds handed over, alive until the call returns
-    d = abi.CloudDesc()
-    d.abi_version = abi.ABI_VERSION
-    d.queries, d.n_queries = _device_cloud(queries, dev, keep)
-    d.targets, d.n_targets = _device_cloud(targets, dev, keep)
-    d.max_dist, d.grid, d.device_id = float(max_dist), int(grid), device_id
-    d2 = torch.empty(d.n_queries, dtype=torch.float32, device=dev)
-    idx = torch.empty(d.n_queries, dtype=torch.int32, device=dev)
-    # (the library works on a stream of its own: the clouds must be complete)
-    torch.cuda.synchronize(dev)
-    counts, ms = (C.c_int64 * 2)(), C.c_float()
-    abi.check(lib, lib.gipuma_hip_cloud_nearest(C.byref(d), d2.data_ptr() if d.n_queries else None,
-                                                idx.data_ptr() if d.n_queries else None, counts, C.byref(ms)),
-              "gipuma_hip_cloud_nearest")
-    out = d2.cpu().numpy(), idx.cpu().numpy(), ms.value
+    torch, lib, d, dev, held = _open("the cloud search", abi.CloudDesc, device_id)
+    d.queries, d.n_queries = _device_cloud(queries, dev, held)
+    d.targets, d.n_targets = _device_cloud(targets, dev, held)
+    d.max_dist, d.grid = float(max_dist), int(grid)
+    d2, idx = (torch.empty(d.n_queries, dtype=t, device=dev) for t in (torch.float32, torch.int32))
+    counts, ms = _call(torch, lib, "gipuma_hip_cloud_nearest", d, dev, (d2, idx), ("found", "none"))
+    out = d2.cpu().numpy(), idx.cpu().numpy(), ms
     if not return_info:
         return out
     stats = (C.c_int64 * len(_STATS))()
     abi.check(lib, lib.gipuma_hip_cloud_last_stats(stats), "gipuma_hip_cloud_last_stats")
-    return out + (dict(found=int(counts[0]), none=int(counts[1]), **{k: int(v) for k, v in zip(_STATS, stats)}),)
+    return out + (dict(counts, **_figures(_STATS, stats)),)
 
 
 def thin_mask(points, radius, seed=0, order="hashed", grid=0, device_id=0):
     """The contract of gipuma_hip_cloud_thin on the (n, 3) cloud `points` (a numpy array or a torch tensor; a device
     tensor is passed by pointer): (keep, device_ms, info) -- keep a torch uint8 tensor on the device, one byte per point,
     info dict(kept, dropped, not_finite, rounds, grid, cells_x, cells_y, cells_z)."""
-    import torch
     if order not in ORDERS:
         raise ValueError("order is 'hashed' or 'index', got %r" % (order,))
-    lib = abi.load_library()
-    if lib.gipuma_hip_device_count() < 1:
-        raise abi.GipumaHipError("thinning a cloud needs a HIP device; gipuma_amd has no CPU fallback")
-    dev, held = torch.device("cuda", device_id), []
-    d = abi.ThinDesc()
-    d.abi_version = abi.ABI_VERSION
+    torch, lib, d, dev, held = _open("thinning a cloud", abi.ThinDesc, device_id)
     d.points, d.n_points = _device_cloud(points, dev, held)
-    d.radius, d.seed, d.order, d.grid, d.device_id = float(radius), int(seed) & 0xFFFFFFFF, ORDERS[order], int(grid), device_id
+    d.radius, d.seed, d.order, d.grid = float(radius), int(seed) & 0xFFFFFFFF, ORDERS[order], int(grid)
     keep = torch.empty(d.n_points, dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize(dev)  # (the library works on a stream of its own: the cloud must be complete)
-    info, ms = (C.c_int64 * len(_THIN_INFO))(), C.c_float()
-    abi.check(lib, lib.gipuma_hip_cloud_thin(C.byref(d), keep.data_ptr() if d.n_points else None, info, C.byref(ms)),
-              "gipuma_hip_cloud_thin")
-    return keep, ms.value, {k: int(v) for k, v in zip(_THIN_INFO, info)}
+    info, ms = _call(torch, lib, "gipuma_hip_cloud_thin", d, dev, (keep,), _THIN_INFO)
+    return keep, ms, info
 
 
 def thin(points, radius, seed=0, order="hashed", grid=0, device_id=0, return_info=False):
@@ -102,10 +110,8 @@ def thin(points, radius, seed=0, order="hashed", grid=0, device_id=0, return_inf
     of seed and index, or with order="index" the caller's own order -- and a point is kept unless a point kept before it
     lies within `radius` (inclusive).  Returns the ascending int64 indices of the kept points (numpy); with return_info
     also device_ms and dict(kept, dropped, not_finite, rounds, grid, cells_x, cells_y, cells_z)."""
-    import torch
     keep, ms, info = thin_mask(points, radius, seed, order, grid, device_id)
-    idx = torch.nonzero(keep).reshape(-1).cpu().numpy().astype(np.int64)
-    return (idx, ms, info) if return_info else idx
+    return (_indices(keep), ms, info) if return_info else _indices(keep)
 
 
 def neighbours(points, radius, min_neighbours=0, max_count=0, grid=0, device_id=0, counts=True, keep=True):
@@ -113,23 +119,13 @@ def neighbours(points, radius, min_neighbours=0, max_count=0, grid=0, device_id=
     tensor is passed by pointer): (count, keep, device_ms, info) -- count a torch int32 tensor on the device holding the
     uint32 counts' bits, keep a torch uint8 tensor on the device, one entry per point each, or None where `counts` /
     `keep` is False; info dict(kept, dropped, not_finite, saturated, grid, cells_x, cells_y, cells_z)."""
-    import torch
-    lib = abi.load_library()
-    if lib.gipuma_hip_device_count() < 1:
-        raise abi.GipumaHipError("counting a cloud's neighbours needs a HIP device; gipuma_amd has no CPU fallback")
-    dev, held = torch.device("cuda", device_id), []
-    d = abi.NeighboursDesc()
-    d.abi_version = abi.ABI_VERSION
+    torch, lib, d, dev, held = _open("counting a cloud's neighbours", abi.NeighboursDesc, device_id)
     d.points, d.n_points = _device_cloud(points, dev, held)
-    d.radius, d.min_neighbours, d.max_count, d.grid, d.device_id = float(radius), int(min_neighbours), int(max_count), int(grid), device_id
+    d.radius, d.min_neighbours, d.max_count, d.grid = float(radius), int(min_neighbours), int(max_count), int(grid)
     count_t = torch.empty(d.n_points, dtype=torch.int32, device=dev) if counts else None
     keep_t = torch.empty(d.n_points, dtype=torch.uint8, device=dev) if keep else None
-    torch.cuda.synchronize(dev)  # (the library works on a stream of its own: the cloud must be complete)
-    info, ms = (C.c_int64 * len(_NEIGHBOUR_INFO))(), C.c_float()
-    abi.check(lib, lib.gipuma_hip_cloud_neighbours(C.byref(d), count_t.data_ptr() if counts and d.n_points else None,
-                                                   keep_t.data_ptr() if keep and d.n_points else None, info, C.byref(ms)),
-              "gipuma_hip_cloud_neighbours")
-    return count_t, keep_t, ms.value, {k: int(v) for k, v in zip(_NEIGHBOUR_INFO, info)}
+    info, ms = _call(torch, lib, "gipuma_hip_cloud_neighbours", d, dev, (count_t, keep_t), _NEIGHBOUR_INFO)
+    return count_t, keep_t, ms, info
 
 
 def neighbour_counts(points, radius, max_count=0, grid=0, device_id=0, return_info=False):
@@ -147,10 +143,8 @@ def drop_isolated(points, radius, min_neighbours, grid=0, device_id=0, return_in
     other finite points lie within `radius` (inclusive).  Counting stops at max(min_neighbours, 1), so points in dense
     regions stop early.  Returns the ascending int64 indices of the kept points (numpy), like `thin`; with return_info also
     device_ms and dict(kept, dropped, not_finite, saturated, grid, cells_x, cells_y, cells_z)."""
-    import torch
     _, keep, ms, info = neighbours(points, radius, min_neighbours, max(int(min_neighbours), 1), grid, device_id, counts=False)
-    idx = torch.nonzero(keep).reshape(-1).cpu().numpy().astype(np.int64)
-    return (idx, ms, info) if return_info else idx
+    return (_indices(keep), ms, info) if return_info else _indices(keep)
 
 
 def direction_score(d2, thresholds):

@@ -25,11 +25,11 @@
 // cell varies from run to run.  The contract's result does not depend on that order: the search carries (d2, j) compared
 // lexicographically, and a cell's points are all visited or all skipped.
 //
-// The same grid has a second client: thinning a cloud to a minimum point spacing (namespace thin below, DESIGN.md 15,
-// gipuma_hip_cloud_thin), the density normalisation that comes before the score.  What both clients do to get the grid
-// is written once, as the host steps at the end of namespace cloud: cloud::Box (the box of a cloud), cloud::lay_out (the
-// grid over a box) and cloud::sort_by_cell (the counting sort).  The exactness arguments of both rest on that one
-// layout: a monotonic cell_of, cells numbered x fastest, ends[] as the scatter leaves them.
+// The same grid has two more clients, on the cloud's own box: thinning it to a minimum point spacing (namespace thin,
+// DESIGN.md 15, gipuma_hip_cloud_thin) and counting each point's neighbours within a radius (namespace support, DESIGN.md
+// 16, gipuma_hip_cloud_neighbours).  What they share is written once in namespace cloud.  Device: d2_of (the contract's
+// d2, the search's too) and Reach (the cells a lane visits and a row's records, with kReach: why no neighbour is skipped).
+// Host: Box, lay_out and sort_by_cell, which the search takes for its targets, and OwnGrid, which runs them for the two.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -39,6 +39,7 @@
 #include "pm_host.h"
 
 using pm_host::fail;
+namespace thin { inline int automatic_grid(float longest, float radius); }  // (the thinning's rule, below; cloud::OwnGrid takes it)
 
 namespace cloud {
 
@@ -74,6 +75,46 @@ __device__ __forceinline__ int cell_of(float p, float lo, float inv_h, int g)
 }
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// The contract's d2 of a point a and a sorted point b, the one place it is written for every client's kernel.
+__device__ __forceinline__ float d2_of(const Rec &a, const Rec &b)
+{
+    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// The reach of a lane's cell range.  Lane a visits, per axis k, the cells cell_of(fl(a_k - reach)) .. cell_of(fl(a_k +
+// reach)) with reach = fl(kReach * radius).  No neighbour is skipped: let b be finite with d2(a, b) <= r2.
+//   * d2 is a sum of non-negative floats and rounding is monotonic, so fl(d_k * d_k) <= d2 <= r2 = fl(radius * radius)
+//     <= radius^2 (1 + 2^-24) for d_k = fl(a_k - b_k).  Either d_k * d_k < 2^-126, and then |d_k| < 2^-63 < radius, or
+//     the product is rounded with relative error 2^-24: d_k^2 <= radius^2 (1 + 2^-24) / (1 - 2^-24).  A difference of
+//     floats never underflows, |a_k - b_k| <= |d_k| / (1 - 2^-24).  Together the REAL |a_k - b_k| <= radius (1 + 2^-22).
+//   * reach >= 1.01 (1 - 2^-24)^2 radius > 1.009 radius (kReach is 1.01 rounded to a float; no underflow, the grid is
+//     only used for 2^-40 <= radius <= 2^40), so the real x = a_k - reach < a_k - radius (1 + 2^-22) <= b_k.  b_k is a
+//     float and rounding is monotonic: b_k >= fl(x), the value the lane computes.  An overflow to -inf only lowers it.
+//   * cell_of is monotonic: cell_of(b_k) >= cell_of(fl(a_k - reach)).  The upper end is the mirror image.
+// Nothing here depends on how cell_of rounds, only on its monotonicity; the slack of 0.9 % is spent on a bound that
+// needs 2^-22.  Outside 2^-40 .. 2^40 (radius or cell edge) the host takes G = 1: one cell, every point visited.
+// The statement is about this range and any finite b within the radius, whatever a client (thin, support) then asks of b.
+constexpr float kReach = 1.01f;
+inline bool reach_holds(float radius) { return radius >= 0x1p-40f && radius <= 0x1p40f; }
+
+struct Reach {
+    int x0, x1, y0, y1, z0, z1;
+
+    __device__ __forceinline__ Reach(const Rec &a, float reach, const Grid &g)
+        : x0(cell_of(a.x - reach, g.lo[0], g.inv_h, g.g[0])), x1(cell_of(a.x + reach, g.lo[0], g.inv_h, g.g[0])),
+          y0(cell_of(a.y - reach, g.lo[1], g.inv_h, g.g[1])), y1(cell_of(a.y + reach, g.lo[1], g.inv_h, g.g[1])),
+          z0(cell_of(a.z - reach, g.lo[2], g.inv_h, g.g[2])), z1(cell_of(a.z + reach, g.lo[2], g.inv_h, g.g[2])) {}
+    // Cells are numbered x fastest and ends[] is what scatter_kernel leaves: the cells x0 .. x1 of the row (y, z) hold the
+    // one contiguous range sorted[beg .. end), as a row of a shell's face does in search_kernel.
+    __device__ __forceinline__ void row(const uint32_t *__restrict__ ends, const Grid &g, int y, int z, uint32_t &beg, uint32_t &end) const
+    {
+        const int c0 = (z * g.g[1] + y) * g.g[0] + x0;
+        end = ends[c0 + (x1 - x0)];
+        beg = c0 ? ends[c0 - 1] : 0u;
+    }
+};
 
 // min of lo[3] / max of hi[3] over the workgroup, left in lane 0's m[]
 __device__ __forceinline__ void reduce_box(float (*s)[kBlock], float m[6])
@@ -243,13 +284,12 @@ __global__ __launch_bounds__(kBlock) void none_kernel(uint32_t n, float *__restr
 // beat nor tie a best_d2 <= threshold, and with threshold >= r2 it is no candidate.  The stop is tested from s = 1 on.
 constexpr float kShellSlack = 0.99f;
 
-__device__ __forceinline__ void visit(const Rec *__restrict__ sorted, uint32_t beg, uint32_t end, float ax, float ay, float az, float r2,
-                                      float &best, int32_t &bj)
+__device__ __forceinline__ void visit(const Rec *__restrict__ sorted, uint32_t beg, uint32_t end, const Rec &a, float r2, float &best,
+                                      int32_t &bj)
 {
     for (uint32_t p = beg; p < end; ++p) {
         const Rec b = sorted[p];
-        const float dx = ax - b.x, dy = ay - b.y, dz = az - b.z;
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const float d2 = d2_of(a, b);
         // A d2 of +inf (an overflow; r2 may be +inf too) is no candidate: +inf means "none" and nothing else.  It never
         // passes d2 < best, and it ties best only while best is still INFINITY, i.e. bj = -1, which no index is below
         // (a SIGNED comparison).  A finite best has bj >= 0: the lowest index wins the tie.
@@ -285,15 +325,15 @@ __global__ __launch_bounds__(kBlock) void search_kernel(const Rec *__restrict__ 
                     const int row = (z * g.g[1] + y) * g.g[0];
                     if (abs(z - cz) == s || abs(y - cy) == s) {
                         const int c0 = row + x0, c1 = row + x1;
-                        visit(targets, c0 ? ends[c0 - 1] : 0u, ends[c1], a.x, a.y, a.z, g.r2, best, bj);
+                        visit(targets, c0 ? ends[c0 - 1] : 0u, ends[c1], a, g.r2, best, bj);
                     } else {  // (s >= 1 here: the two ends are different cells)
                         if (cx - s >= 0) {
                             const int c = row + cx - s;
-                            visit(targets, c ? ends[c - 1] : 0u, ends[c], a.x, a.y, a.z, g.r2, best, bj);
+                            visit(targets, c ? ends[c - 1] : 0u, ends[c], a, g.r2, best, bj);
                         }
                         if (cx + s <= g.g[0] - 1) {
                             const int c = row + cx + s;
-                            visit(targets, ends[c - 1], ends[c], a.x, a.y, a.z, g.r2, best, bj);
+                            visit(targets, ends[c - 1], ends[c], a, g.r2, best, bj);
                         }
                     }
                 }
@@ -409,6 +449,43 @@ int sort_by_cell(hipStream_t st, const float *pts, uint32_t n, const Layout &l, 
     return 0;
 }
 
+// A cloud sorted on a grid over its OWN box: the host set-up of the thinning and the neighbour count.  The steps are calls of
+// their own, as Box's are, so that a caller's event and its own memsets keep their places on the stream.
+struct OwnGrid {
+    Box box;        // (the caller allocates it, before its first event)
+    Layout l = {};  // (the report stays 0 where no point is finite)
+    bool any = false;
+    Rec *sorted = nullptr;
+    uint32_t *cells = nullptr, *counters = nullptr;
+    int32_t *cellid = nullptr;
+
+    // the box kernels and the host's read; where a point is finite (`any`) the layout (thin's automatic G for grid 0, one
+    // cell unless reach_holds), the buffers and the memsets of the cells and of the caller's n_counters counters
+    int lay(pm_host::CallScope &sc, const float *pts, uint32_t n, float radius, int grid, int n_counters)
+    {
+        if (const int rc = box.enqueue(sc.st, pts, n)) return rc;
+        if (const int rc = box.read(sc.st)) return rc;
+        if (!(any = box.any_finite())) return 0;
+        l = lay_out(box, grid ? grid : thin::automatic_grid(box.longest_extent(), radius), radius * radius, reach_holds(radius));
+        if (sc.alloc(cells, l.ncells) || sc.alloc(counters, n_counters) || sc.alloc(cellid, n) || sc.alloc(sorted, n))
+            return GIPUMA_HIP_ERR_DEVICE;
+        HIP_OK(hipMemsetAsync(cells, 0, sizeof(uint32_t) * l.ncells, sc.st));
+        HIP_OK(hipMemsetAsync(counters, 0, sizeof(uint32_t) * n_counters, sc.st));
+        return 0;
+    }
+    // the counting sort: cells[] goes out as the cells' ends, counters[kTargets] as the number of finite points
+    int sort(hipStream_t st, const float *pts, uint32_t n) const
+    {
+        return sort_by_cell<false>(st, pts, n, l, cellid, cells, sorted, nullptr, nullptr, counters, nullptr);
+    }
+    // info[8] of both calls: kept, dropped, not finite, the caller's fourth figure, G, cells x, y, z
+    void report(int64_t info[8], uint32_t n, uint32_t finite, uint32_t kept, uint32_t fourth) const
+    {
+        const int64_t figures[4] = {kept, (int64_t)finite - kept, (int64_t)n - finite, fourth};
+        if (info) memcpy(info, figures, sizeof figures), memcpy(info + 4, l.report, sizeof l.report);
+    }
+};
+
 }  // namespace cloud
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -418,13 +495,11 @@ int sort_by_cell(hipStream_t st, const float *pts, uint32_t n, const Layout &l, 
 // radius graph.  A point that is not finite is never kept and never suppresses.
 //
 // Launches, all on one stream:
-//   cloud::box_*, count_kernel<false>, scan_kernel, scatter_kernel    the box of the finite points and their counting sort
-//                                                  by cell, once, through the steps the search takes for its targets:
-//                                                  cloud::Box, cloud::lay_out, cloud::sort_by_cell<false>
+//   cloud::OwnGrid (box_*, count_kernel<false>, scan_kernel, scatter_kernel)   the finite points sorted by cell, once
 //   thin::round_kernel, once per round t = 1, 2, ...   one lane per UNDECIDED point, taken from a worklist of sorted
-//                                                  positions; survivors are appended to the other worklist (one ballot
-//                                                  and one atomicAdd per wavefront); the host reads the 4-byte survivor
-//                                                  count and sizes the next launch
+//                                                  positions, over the cells of its cloud::Reach; survivors are appended
+//                                                  to the other worklist (one ballot and one atomicAdd per wavefront);
+//                                                  the host reads the 4-byte survivor count and sizes the next launch
 // One uint32 of state per SORTED POSITION (a cell's states are contiguous, like its records): 0 = undecided, a point
 // decided in round t stores 2t + kept.  In round t a reader takes a state s for decided only if (s >> 1) < t: a value
 // stored in the current round reads as undecided whether or not the reader sees it, so the in-place plain stores give
@@ -440,34 +515,16 @@ int sort_by_cell(hipStream_t st, const float *pts, uint32_t n, const Layout &l, 
 // ---------------------------------------------------------------------------------------------------------------------
 namespace thin {
 
-using cloud::cell_of;
-using cloud::Grid;
-using cloud::kBlock;
-using cloud::Rec;
+using namespace cloud;  // (Rec, Grid, Reach, d2_of, kBlock)
 
 enum { kKept = cloud::kStats, kSurvivors, kCounters };  // the device counters, behind cloud's (kTargets: the finite points)
-
-// The reach of a lane's cell range.  Lane a visits, per axis k, the cells cell_of(fl(a_k - reach)) .. cell_of(fl(a_k +
-// reach)) with reach = fl(kReach * radius).  No neighbour is skipped: let b be finite with d2(a, b) <= r2.
-//   * d2 is a sum of non-negative floats and rounding is monotonic, so fl(d_k * d_k) <= d2 <= r2 = fl(radius * radius)
-//     <= radius^2 (1 + 2^-24) for d_k = fl(a_k - b_k).  Either d_k * d_k < 2^-126, and then |d_k| < 2^-63 < radius, or
-//     the product is rounded with relative error 2^-24: d_k^2 <= radius^2 (1 + 2^-24) / (1 - 2^-24).  A difference of
-//     floats never underflows, |a_k - b_k| <= |d_k| / (1 - 2^-24).  Together the REAL |a_k - b_k| <= radius (1 + 2^-22).
-//   * reach >= 1.01 (1 - 2^-24)^2 radius > 1.009 radius (kReach is 1.01 rounded to a float; no underflow, the grid is
-//     only used for 2^-40 <= radius <= 2^40), so the real x = a_k - reach < a_k - radius (1 + 2^-22) <= b_k.  b_k is a
-//     float and rounding is monotonic: b_k >= fl(x), the value the lane computes.  An overflow to -inf only lowers it.
-//   * cell_of is monotonic: cell_of(b_k) >= cell_of(fl(a_k - reach)).  The upper end is the mirror image.
-// Nothing here depends on how cell_of rounds, only on its monotonicity; the slack of 0.9 % is spent on a bound that
-// needs 2^-22.  Outside 2^-40 .. 2^40 (radius or cell edge) the host takes G = 1: one cell, every point visited.
-constexpr float kReach = 1.01f;
 
 // prio(i) of the hashed order: mix32(mix32(seed + 0x9E3779B9) ^ (i + 0x85EBCA6B)); salt is the inner mix32, from the host.
 using pm::mix32;
 __device__ __forceinline__ uint32_t prio_of(int32_t i, uint32_t salt, bool hashed) { return hashed ? mix32(salt ^ ((uint32_t)i + 0x85EBCA6BU)) : 0u; }
 
 // One round.  n_in undecided points: the sorted positions list_in[0 .. n_in), or 0 .. n_in itself when list_in is null
-// (round 1: every sorted point).  Cells are numbered x fastest: the cells x0 .. x1 of one (y, z) row are one contiguous
-// range of sorted records, as in cloud::search_kernel.
+// (round 1: every sorted point).
 __global__ __launch_bounds__(kBlock) void round_kernel(const Rec *__restrict__ sorted, const uint32_t *__restrict__ ends, Grid g, float reach,
                                                        uint32_t salt, int hashed, uint32_t round, uint32_t *state,
                                                        const uint32_t *__restrict__ list_in, uint32_t n_in,
@@ -481,19 +538,14 @@ __global__ __launch_bounds__(kBlock) void round_kernel(const Rec *__restrict__ s
         pos = list_in ? list_in[t] : t;
         const Rec a = sorted[pos];
         const uint32_t pa = prio_of(a.j, salt, hashed);
-        const int x0 = cell_of(a.x - reach, g.lo[0], g.inv_h, g.g[0]), x1 = cell_of(a.x + reach, g.lo[0], g.inv_h, g.g[0]);
-        const int y0 = cell_of(a.y - reach, g.lo[1], g.inv_h, g.g[1]), y1 = cell_of(a.y + reach, g.lo[1], g.inv_h, g.g[1]);
-        const int z0 = cell_of(a.z - reach, g.lo[2], g.inv_h, g.g[2]), z1 = cell_of(a.z + reach, g.lo[2], g.inv_h, g.g[2]);
+        const Reach r(a, reach, g);
         bool dropped = false, blocked = false;
-        for (int z = z0; z <= z1 && !dropped; ++z)
-            for (int y = y0; y <= y1 && !dropped; ++y) {
-                const int c0 = (z * g.g[1] + y) * g.g[0] + x0, c1 = c0 + (x1 - x0);
-                const uint32_t end = ends[c1];
-                for (uint32_t p = c0 ? ends[c0 - 1] : 0u; p < end; ++p) {
+        for (int z = r.z0; z <= r.z1 && !dropped; ++z)
+            for (int y = r.y0; y <= r.y1 && !dropped; ++y) {
+                uint32_t p, end;
+                for (r.row(ends, g, y, z, p, end); p < end; ++p) {
                     const Rec b = sorted[p];
-                    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    if (!(d2 <= g.r2) || p == pos) continue;
+                    if (!(d2_of(a, b) <= g.r2) || p == pos) continue;
                     const uint32_t pb = prio_of(b.j, salt, hashed);
                     if (!(pb < pa || (pb == pa && b.j < a.j))) continue;  // (only lower keys decide about a)
                     const uint32_t s = state[p];
@@ -544,20 +596,15 @@ inline int automatic_grid(float longest, float radius)
 // does not depend on the order the records are visited in.
 //
 // Launches, all on one stream:
-//   cloud::box_*, count_kernel<false>, scan_kernel, scatter_kernel    the thinning's set-up, through the same host steps:
-//                                                  cloud::Box, cloud::lay_out (thin::automatic_grid), cloud::sort_by_cell<false>
-//   support::count_kernel, once                    one lane per sorted position over the thinning's cell range (thin::kReach:
-//                                                  its derivation is why no neighbour is skipped here either); the lane's
-//                                                  counter goes to the caller's index
+//   cloud::OwnGrid (box_*, count_kernel<false>, scan_kernel, scatter_kernel)   the thinning's set-up
+//   support::count_kernel, once                    one lane per sorted position over the cells of its cloud::Reach, the
+//                                                  thinning's range; the lane's counter goes to the caller's index
 // The lanes of a wavefront are neighbours in the sorted order: they stand in the same or in adjacent cells, walk the same
 // rows and load the same records, which the vector cache serves once per wavefront.  There is no LDS staging.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace support {
 
-using cloud::cell_of;
-using cloud::Grid;
-using cloud::kBlock;
-using cloud::Rec;
+using namespace cloud;  // (Rec, Grid, Reach, d2_of, kBlock)
 
 enum { kKept = cloud::kStats, kSaturated, kCounters };  // the device counters, behind cloud's (kTargets: the finite points)
 
@@ -573,19 +620,14 @@ __global__ __launch_bounds__(kBlock) void count_kernel(const Rec *__restrict__ s
     bool kept = false, full = false;
     if (pos < *n_sorted) {
         const Rec a = sorted[pos];
-        const int x0 = cell_of(a.x - reach, g.lo[0], g.inv_h, g.g[0]), x1 = cell_of(a.x + reach, g.lo[0], g.inv_h, g.g[0]);
-        const int y0 = cell_of(a.y - reach, g.lo[1], g.inv_h, g.g[1]), y1 = cell_of(a.y + reach, g.lo[1], g.inv_h, g.g[1]);
-        const int z0 = cell_of(a.z - reach, g.lo[2], g.inv_h, g.g[2]), z1 = cell_of(a.z + reach, g.lo[2], g.inv_h, g.g[2]);
+        const Reach r(a, reach, g);
         uint32_t count = 0;
-        for (int z = z0; z <= z1 && !full; ++z)
-            for (int y = y0; y <= y1 && !full; ++y) {
-                const int c0 = (z * g.g[1] + y) * g.g[0] + x0, c1 = c0 + (x1 - x0);
-                const uint32_t end = ends[c1];
-                for (uint32_t p = c0 ? ends[c0 - 1] : 0u; p < end; ++p) {
+        for (int z = r.z0; z <= r.z1 && !full; ++z)
+            for (int y = r.y0; y <= r.y1 && !full; ++y) {
+                uint32_t p, end;
+                for (r.row(ends, g, y, z, p, end); p < end; ++p) {
                     const Rec b = sorted[p];
-                    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    if (d2 <= g.r2 && p != pos && ++count == max_count) {
+                    if (d2_of(a, b) <= g.r2 && p != pos && ++count == max_count) {
                         full = true;
                         break;
                     }
@@ -687,68 +729,49 @@ int run_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int64_t info[8], 
     pm_host::CallScope sc;
     if (const int rc = sc.open(d->stream, 2)) return rc;
     hipStream_t st = sc.st;
-    int64_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kept, dropped, not finite, rounds, G, cells x, y, z
+    cloud::OwnGrid og;
+    uint32_t finite = 0, kept = 0, rounds = 0;
     float ms = 0.f;
 
     if (n) {
-        // the mask comes out of the rounds with the kept points set; the box of the finite points
-        cloud::Box box;
-        if (const int rc = box.alloc(sc, n)) return rc;
+        // the mask comes out of the rounds with the kept points set
+        if (const int rc = og.box.alloc(sc, n)) return rc;
         HIP_OK(hipEventRecord(sc.e[0], st));
         HIP_OK(hipMemsetAsync(keep_dev, 0, n, st));
-        if (const int rc = box.enqueue(st, d->points, n)) return rc;
-        if (const int rc = box.read(st)) return rc;
-
-        uint32_t finite = 0, kept = 0, rounds = 0;
-        if (box.any_finite()) {  // (else: nothing is kept)
-            // the grid; the derivation of thin::kReach does not hold for a radius outside 2^-40 .. 2^40
-            const cloud::Layout l = cloud::lay_out(box, d->grid ? d->grid : thin::automatic_grid(box.longest_extent(), d->radius),
-                                                   d->radius * d->radius, d->radius >= 0x1p-40f && d->radius <= 0x1p40f);
-            memcpy(out + 4, l.report, sizeof l.report);
-
-            uint32_t *cells, *counters, *state, *list[2];
-            int32_t *cellid;
-            cloud::Rec *sorted;
-            if (sc.alloc(cells, l.ncells) || sc.alloc(counters, thin::kCounters) || sc.alloc(cellid, n) || sc.alloc(sorted, n) ||
-                sc.alloc(state, n) || sc.alloc(list[0], n) || sc.alloc(list[1], n))
-                return GIPUMA_HIP_ERR_DEVICE;
-            HIP_OK(hipMemsetAsync(cells, 0, sizeof(uint32_t) * l.ncells, st));
-            HIP_OK(hipMemsetAsync(counters, 0, sizeof(uint32_t) * thin::kCounters, st));
+        if (const int rc = og.lay(sc, d->points, n, d->radius, d->grid, thin::kCounters)) return rc;
+        if (og.any) {  // (else: nothing is kept)
+            uint32_t *state, *list[2];
+            if (sc.alloc(state, n) || sc.alloc(list[0], n) || sc.alloc(list[1], n)) return GIPUMA_HIP_ERR_DEVICE;
             HIP_OK(hipMemsetAsync(state, 0, sizeof(uint32_t) * n, st));
-            if (const int rc = cloud::sort_by_cell<false>(st, d->points, n, l, cellid, cells, sorted, nullptr, nullptr, counters, nullptr))
-                return rc;
-            HIP_OK(hipMemcpyAsync(&finite, counters + cloud::kTargets, sizeof finite, hipMemcpyDeviceToHost, st));
+            if (const int rc = og.sort(st, d->points, n)) return rc;
+            HIP_OK(hipMemcpyAsync(&finite, og.counters + cloud::kTargets, sizeof finite, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
-
             // the rounds: the host reads the survivor count after each and sizes the next launch with it
-            const float reach = thin::kReach * d->radius;
+            const float reach = cloud::kReach * d->radius;
             const uint32_t salt = pm::mix32(d->seed + 0x9E3779B9U);
             uint32_t undecided = finite;
             while (undecided) {
                 ++rounds;
                 uint32_t survivors = 0;
-                HIP_OK(hipMemsetAsync(counters + thin::kSurvivors, 0, sizeof(uint32_t), st));
-                hipLaunchKernelGGL(thin::round_kernel, cloud::blocks_for(undecided), dim3(cloud::kBlock), 0, st, sorted, cells, l.g, reach,
-                                   salt, d->order == 0 ? 1 : 0, rounds, state, rounds == 1 ? (const uint32_t *)nullptr : list[rounds & 1],
-                                   undecided, list[(rounds + 1) & 1], counters, keep_dev);
+                HIP_OK(hipMemsetAsync(og.counters + thin::kSurvivors, 0, sizeof(uint32_t), st));
+                hipLaunchKernelGGL(thin::round_kernel, cloud::blocks_for(undecided), dim3(cloud::kBlock), 0, st, og.sorted, og.cells,
+                                   og.l.g, reach, salt, d->order == 0 ? 1 : 0, rounds, state,
+                                   rounds == 1 ? (const uint32_t *)nullptr : list[rounds & 1], undecided, list[(rounds + 1) & 1],
+                                   og.counters, keep_dev);
                 HIP_OK(hipGetLastError());
-                HIP_OK(hipMemcpyAsync(&survivors, counters + thin::kSurvivors, sizeof survivors, hipMemcpyDeviceToHost, st));
+                HIP_OK(hipMemcpyAsync(&survivors, og.counters + thin::kSurvivors, sizeof survivors, hipMemcpyDeviceToHost, st));
                 HIP_OK(hipStreamSynchronize(st));
                 if (survivors >= undecided)  // (the lowest-key undecided point is always decided: this bounds the loop)
                     return fail(GIPUMA_HIP_ERR_DEVICE, "thin: round %u decided none of its %u undecided points", rounds, undecided);
                 undecided = survivors;
             }
-            HIP_OK(hipMemcpyAsync(&kept, counters + thin::kKept, sizeof kept, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(&kept, og.counters + thin::kKept, sizeof kept, hipMemcpyDeviceToHost, st));
         }
         HIP_OK(hipEventRecord(sc.e[1], st));
         HIP_OK(hipStreamSynchronize(st));
         HIP_OK(hipEventElapsedTime(&ms, sc.e[0], sc.e[1]));
-        out[0] = kept;
-        out[1] = (int64_t)finite - kept;
-        out[2] = (int64_t)n - finite;
-        out[3] = rounds;
     }
-    if (info) memcpy(info, out, sizeof out);
+    og.report(info, n, finite, kept, rounds);
     if (device_ms) *device_ms = ms;
     return 0;
 }
@@ -760,52 +783,47 @@ int run_neighbours(const gipuma_hip_neighbours_desc *d, uint32_t *count_dev, uin
     pm_host::CallScope sc;
     if (const int rc = sc.open(d->stream, 2)) return rc;
     hipStream_t st = sc.st;
-    int64_t out[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // kept, dropped, not finite, saturated, G, cells x, y, z
+    cloud::OwnGrid og;
+    uint32_t counters[support::kCounters] = {};
     float ms = 0.f;
 
     if (n) {
-        // both outputs come out of the kernel with the finite points' entries written; the box of the finite points
-        cloud::Box box;
-        if (const int rc = box.alloc(sc, n)) return rc;
+        // both outputs come out of the kernel with the finite points' entries written
+        if (const int rc = og.box.alloc(sc, n)) return rc;
         HIP_OK(hipEventRecord(sc.e[0], st));
         if (count_dev) HIP_OK(hipMemsetAsync(count_dev, 0, sizeof(uint32_t) * n, st));
         if (keep_dev) HIP_OK(hipMemsetAsync(keep_dev, 0, n, st));
-        if (const int rc = box.enqueue(st, d->points, n)) return rc;
-        if (const int rc = box.read(st)) return rc;
-
-        uint32_t counters[support::kCounters] = {};
-        if (box.any_finite()) {  // (else: nothing is counted, nothing kept)
-            // the thinning's grid, on the thinning's condition: thin::kReach is derived for a radius in 2^-40 .. 2^40
-            const cloud::Layout l = cloud::lay_out(box, d->grid ? d->grid : thin::automatic_grid(box.longest_extent(), d->radius),
-                                                   d->radius * d->radius, d->radius >= 0x1p-40f && d->radius <= 0x1p40f);
-            memcpy(out + 4, l.report, sizeof l.report);
-
-            uint32_t *cells, *counters_dev;
-            int32_t *cellid;
-            cloud::Rec *sorted;
-            if (sc.alloc(cells, l.ncells) || sc.alloc(counters_dev, support::kCounters) || sc.alloc(cellid, n) || sc.alloc(sorted, n))
-                return GIPUMA_HIP_ERR_DEVICE;
-            HIP_OK(hipMemsetAsync(cells, 0, sizeof(uint32_t) * l.ncells, st));
-            HIP_OK(hipMemsetAsync(counters_dev, 0, sizeof counters, st));
-            if (const int rc = cloud::sort_by_cell<false>(st, d->points, n, l, cellid, cells, sorted, nullptr, nullptr, counters_dev, nullptr))
-                return rc;
-            hipLaunchKernelGGL(support::count_kernel, cloud::blocks_for(n), dim3(cloud::kBlock), 0, st, sorted, cells,
-                               counters_dev + cloud::kTargets, l.g, thin::kReach * d->radius, (uint32_t)d->max_count,
-                               (uint32_t)d->min_neighbours, count_dev, keep_dev, counters_dev);
+        if (const int rc = og.lay(sc, d->points, n, d->radius, d->grid, support::kCounters)) return rc;
+        if (og.any) {  // (else: nothing is counted, nothing kept)
+            if (const int rc = og.sort(st, d->points, n)) return rc;
+            hipLaunchKernelGGL(support::count_kernel, cloud::blocks_for(n), dim3(cloud::kBlock), 0, st, og.sorted, og.cells,
+                               og.counters + cloud::kTargets, og.l.g, cloud::kReach * d->radius, (uint32_t)d->max_count,
+                               (uint32_t)d->min_neighbours, count_dev, keep_dev, og.counters);
             HIP_OK(hipGetLastError());
-            HIP_OK(hipMemcpyAsync(counters, counters_dev, sizeof counters, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(counters, og.counters, sizeof counters, hipMemcpyDeviceToHost, st));
         }
         HIP_OK(hipEventRecord(sc.e[1], st));
         HIP_OK(hipStreamSynchronize(st));
         HIP_OK(hipEventElapsedTime(&ms, sc.e[0], sc.e[1]));
-        out[0] = counters[support::kKept];
-        out[1] = (int64_t)counters[cloud::kTargets] - counters[support::kKept];
-        out[2] = (int64_t)n - counters[cloud::kTargets];
-        out[3] = counters[support::kSaturated];
     }
-    if (info) memcpy(info, out, sizeof out);
+    og.report(info, n, counters[cloud::kTargets], counters[support::kKept], counters[support::kSaturated]);
     if (device_ms) *device_ms = ms;
     return 0;
+}
+
+// The checks the three entry points share, in their order, `what` before every text.  null_pointer: the entry point's own
+// rule; own: the text of the first of its own checks that fails (null: none), reported in its place.  The device comes last.
+int check_args(const char *what, int abi_version, int64_t n0, int64_t n1, bool null_pointer, const char *dist_name, float dist,
+               const char *own, int grid, int device_id)
+{
+    if (abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "%s: abi_version mismatch", what);
+    if (n0 < 0 || n1 < 0) return fail(GIPUMA_HIP_ERR_ARG, "%s: negative point count", what);
+    if ((n0 | n1) >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "%s: a cloud may hold at most 2^31 - 1 points", what);
+    if (null_pointer) return fail(GIPUMA_HIP_ERR_ARG, "%s: null pointer with a non-zero point count", what);
+    if (!(dist > 0.f) || !std::isfinite(dist)) return fail(GIPUMA_HIP_ERR_ARG, "%s: %s must be > 0 and finite", what, dist_name);
+    if (own) return fail(GIPUMA_HIP_ERR_ARG, "%s: %s", what, own);
+    if (grid < 0 || grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "%s: grid must be 0 (automatic) or 1..256", what);
+    return pm_host::check_device(device_id);
 }
 
 }  // namespace
@@ -815,15 +833,10 @@ extern "C" {
 int gipuma_hip_cloud_nearest(const gipuma_hip_cloud_desc *d, float *d2_dev, int32_t *idx_dev, int64_t counts[2], float *device_ms)
 {
     if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
-    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "cloud: abi_version mismatch");
-    if (d->n_queries < 0 || d->n_targets < 0) return fail(GIPUMA_HIP_ERR_ARG, "cloud: negative point count");
-    if (d->n_queries >= (1ll << 31) || d->n_targets >= (1ll << 31))
-        return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "cloud: a cloud may hold at most 2^31 - 1 points");
-    if ((d->n_queries && (!d->queries || !d2_dev || !idx_dev)) || (d->n_targets && !d->targets))
-        return fail(GIPUMA_HIP_ERR_ARG, "cloud: null pointer with a non-zero point count");
-    if (!(d->max_dist > 0.f) || !std::isfinite(d->max_dist)) return fail(GIPUMA_HIP_ERR_ARG, "cloud: max_dist must be > 0 and finite");
-    if (d->grid < 0 || d->grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "cloud: grid must be 0 (automatic) or 1..256");
-    if (const int rc = pm_host::check_device(d->device_id)) return rc;
+    if (const int rc = check_args("cloud", d->abi_version, d->n_queries, d->n_targets,
+                                  (d->n_queries && (!d->queries || !d2_dev || !idx_dev)) || (d->n_targets && !d->targets), "max_dist",
+                                  d->max_dist, nullptr, d->grid, d->device_id))
+        return rc;
     memset(last_stats, 0, sizeof last_stats);
     return run(d, d2_dev, idx_dev, counts, device_ms);
 }
@@ -838,14 +851,10 @@ int gipuma_hip_cloud_last_stats(int64_t stats[6])
 int gipuma_hip_cloud_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int64_t info[8], float *device_ms)
 {
     if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
-    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "thin: abi_version mismatch");
-    if (d->n_points < 0) return fail(GIPUMA_HIP_ERR_ARG, "thin: negative point count");
-    if (d->n_points >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "thin: a cloud may hold at most 2^31 - 1 points");
-    if (d->n_points && (!d->points || !keep_dev)) return fail(GIPUMA_HIP_ERR_ARG, "thin: null pointer with a non-zero point count");
-    if (!(d->radius > 0.f) || !std::isfinite(d->radius)) return fail(GIPUMA_HIP_ERR_ARG, "thin: radius must be > 0 and finite");
-    if (d->order != 0 && d->order != 1) return fail(GIPUMA_HIP_ERR_ARG, "thin: order must be 0 (hashed) or 1 (index)");
-    if (d->grid < 0 || d->grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "thin: grid must be 0 (automatic) or 1..256");
-    if (const int rc = pm_host::check_device(d->device_id)) return rc;
+    const char *own = d->order != 0 && d->order != 1 ? "order must be 0 (hashed) or 1 (index)" : nullptr;
+    if (const int rc = check_args("thin", d->abi_version, d->n_points, 0, d->n_points && (!d->points || !keep_dev), "radius", d->radius,
+                                  own, d->grid, d->device_id))
+        return rc;
     return run_thin(d, keep_dev, info, device_ms);
 }
 
@@ -853,18 +862,12 @@ int gipuma_hip_cloud_neighbours(const gipuma_hip_neighbours_desc *d, uint32_t *c
                                 float *device_ms)
 {
     if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
-    if (d->abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: abi_version mismatch");
-    if (d->n_points < 0) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: negative point count");
-    if (d->n_points >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "neighbours: a cloud may hold at most 2^31 - 1 points");
-    if (d->n_points && (!d->points || (!count_dev && !keep_dev)))
-        return fail(GIPUMA_HIP_ERR_ARG, "neighbours: null pointer with a non-zero point count");
-    if (!(d->radius > 0.f) || !std::isfinite(d->radius)) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: radius must be > 0 and finite");
-    if (d->min_neighbours < 0) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: min_neighbours must be >= 0");
-    if (d->max_count < 0) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: max_count must be >= 0 (0: exact counts)");
-    if (d->max_count > 0 && d->min_neighbours > d->max_count)
-        return fail(GIPUMA_HIP_ERR_ARG, "neighbours: min_neighbours must not exceed a max_count > 0");
-    if (d->grid < 0 || d->grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "neighbours: grid must be 0 (automatic) or 1..256");
-    if (const int rc = pm_host::check_device(d->device_id)) return rc;
+    const char *own = d->min_neighbours < 0 ? "min_neighbours must be >= 0"
+                      : d->max_count < 0    ? "max_count must be >= 0 (0: exact counts)"
+                      : d->max_count > 0 && d->min_neighbours > d->max_count ? "min_neighbours must not exceed a max_count > 0" : nullptr;
+    if (const int rc = check_args("neighbours", d->abi_version, d->n_points, 0, d->n_points && (!d->points || (!count_dev && !keep_dev)),
+                                  "radius", d->radius, own, d->grid, d->device_id))
+        return rc;
     return run_neighbours(d, count_dev, keep_dev, info, device_ms);
 }
 
