@@ -37,7 +37,11 @@ MI355X-first differences from the shell loop:
     first, as DTU's evaluation does (DESIGN.md 15);
   * --fuse_neighbour_radius r --fuse_min_neighbours N (with --fuse): the fused cloud loses its isolated points -- those
     with fewer than N other points within r (gipuma_amd.cloud_eval.drop_isolated) -- before fused.ply is
-    written and before --eval_cloud scores it.
+    written and before --eval_cloud scores it;
+  * --fuse_outlier_radius r --fuse_outlier_k K --fuse_outlier_std s (with --fuse): the fused cloud then loses its
+    statistical outliers -- the points whose mean distance to their K nearest neighbours within r exceeds the cloud's
+    mean of that figure by more than s standard deviations, and those with fewer than K neighbours there (DESIGN.md 17,
+    gipuma_amd.cloud_eval.drop_outliers) -- after --fuse_neighbour_radius, before fused.ply is written and scored.
 
 Images: what the reference's scripts hand to imread (main.cpp:739-751) -- PNG, JPG (through PIL), binary PGM / PPM.
 Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
@@ -331,6 +335,14 @@ def parse_args(argv):
                          "points within this radius, before fused.ply is written and scored (0: off; DESIGN.md 16)")
     pa.add_argument("--fuse_min_neighbours", type=int, default=None,
                     help="with --fuse_neighbour_radius: the count a fused point needs to stay")
+    pa.add_argument("--fuse_outlier_radius", type=float, default=0.0,
+                    help="with --fuse, --fuse_outlier_k and --fuse_outlier_std: after --fuse_neighbour_radius, drop the fused "
+                         "points whose mean distance to their k nearest neighbours within this radius is above the cloud's "
+                         "mean of it by more than that many standard deviations, and those with fewer than k neighbours "
+                         "there (0: off; DESIGN.md 17)")
+    pa.add_argument("--fuse_outlier_k", type=int, default=None, help="with --fuse_outlier_radius: the number of nearest neighbours, 1..32")
+    pa.add_argument("--fuse_outlier_std", type=float, default=None,
+                    help="with --fuse_outlier_radius: the standard deviations allowed, >= 0")
     args = pa.parse_args(argv)
     # the reference parses these with sscanf("%f") into float fields (main.cpp:300-360)
     for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
@@ -353,6 +365,10 @@ def parse_args(argv):
     if args.fuse_neighbour_radius > 0 and not args.fuse:
         pa.error("--fuse_neighbour_radius filters the fused cloud: it needs --fuse")
     args.fuse_min_neighbours = args.fuse_min_neighbours or 0
+    from .cloud_eval import check_outlier_args
+    check_outlier_args(pa, args, "fuse_outlier_radius", "fuse_outlier_k", "fuse_outlier_std")
+    if args.fuse_outlier_radius > 0 and not args.fuse:
+        pa.error("--fuse_outlier_radius filters the fused cloud: it needs --fuse")
     if args.levels < 1:
         raise SystemExit("--levels must be >= 1")
     args.level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
@@ -393,6 +409,13 @@ def fuse_solved(scan):
         kept, ms, _ = cloud_eval.drop_isolated(np.stack([points["x"], points["y"], points["z"]], axis=-1), args.fuse_neighbour_radius,
                                                args.fuse_min_neighbours, device_id=scan.dev[0].device.index, return_info=True)
         filtered = {"points_before_filter": int(len(points)), "filter_device_ms": ms}
+        points = points[kept]
+    if args.fuse_outlier_radius > 0:  # (then the statistical outliers, of the cloud the count has cleaned)
+        from . import cloud_eval
+        kept, ms, o = cloud_eval.drop_outliers(np.stack([points["x"], points["y"], points["z"]], axis=-1), args.fuse_outlier_radius,
+                                               args.fuse_outlier_k, args.fuse_outlier_std, device_id=scan.dev[0].device.index,
+                                               return_info=True)
+        filtered.update({"points_before_outliers": int(len(points)), "outlier_threshold": o["threshold"], "outlier_device_ms": ms})
         points = points[kept]
     dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
     scan.fused_xyz = np.stack([points["x"], points["y"], points["z"]], axis=-1)  # (for --eval_cloud)

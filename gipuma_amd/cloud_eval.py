@@ -1,8 +1,10 @@
 """Score a point cloud against a reference cloud on the GPU: accuracy and completeness, after thinning
-the cloud to a minimum point spacing and dropping its isolated points when asked to.
+the cloud to a minimum point spacing, dropping its isolated points and dropping its
+statistical outliers when asked to.
 
     python -m gipuma_amd.cloud_eval --cloud fused.ply --reference gt.ply --max_dist 20 --thresholds 0.5,1,2 \\
         [--reduce 0.2 [--reduce_reference] [--seed N]] [--neighbour_radius 1 --min_neighbours 8] \\
+        [--outlier_radius 1 --outlier_k 16 --outlier_std 2] \\
         [--write_cloud scored.ply] [--output report.json]
 
 DTU -- the data set this project is calibrated on -- scores a reconstruction cloud against cloud: accuracy is the distance
@@ -15,8 +17,12 @@ to sample each surface; DTU removes that by thinning the reconstruction to a min
 within the spacing), and `thin` offers it for the delivered cloud.  What a fused cloud still carries then are floaters:
 points, or small clumps of points, far from any surface.  --neighbour_radius / --min_neighbours drop every point with
 fewer than that many other points within the radius (gipuma_hip_cloud_neighbours; `drop_isolated`, `neighbour_counts`),
-after the thinning: a count means the same everywhere only once the density is normalised.  --write_cloud writes the cloud
-as it is scored.  Not part of the score here: DTU's observability masks and ground-plane removal.
+after the thinning: a count means the same everywhere only once the density is normalised.  A count cannot see the loose
+halo a few spacings off a surface, or the smeared rim of a depth step: such points have neighbours enough, only farther away
+than a surface point's.  --outlier_radius / --outlier_k / --outlier_std drop every point whose mean distance to its k
+nearest neighbours within the radius (gipuma_hip_cloud_knn; `knn`, `nearest_k`, `drop_outliers`) exceeds the cloud's mean of
+that figure by more than outlier_std standard deviations, and every point with fewer than k neighbours there.  --write_cloud
+writes the cloud as it is scored.  Not part of the score here: DTU's observability masks and ground-plane removal.
 """
 import argparse
 import ctypes as C
@@ -31,6 +37,7 @@ THRESHOLDS = (0.5, 1.0, 2.0)
 _STATS = ("grid", "cells_x", "cells_y", "cells_z", "early_out", "searched")
 ORDERS = {"hashed": 0, "index": 1}
 _THIN_INFO = ("kept", "dropped", "not_finite", "rounds", "grid", "cells_x", "cells_y", "cells_z")
+_KNN_INFO = ("complete", "short", "not_finite", "unused", "grid", "cells_x", "cells_y", "cells_z")
 _NEIGHBOUR_INFO = ("kept", "dropped", "not_finite", "saturated", "grid", "cells_x", "cells_y", "cells_z")
 
 
@@ -147,6 +154,71 @@ def drop_isolated(points, radius, min_neighbours, grid=0, device_id=0, return_in
     return (_indices(keep), ms, info) if return_info else _indices(keep)
 
 
+def knn(points, radius, k, grid=0, device_id=0, d2=True, idx=True, count=True, mean=True):
+    """The contract of gipuma_hip_cloud_knn on the (n, 3) cloud `points` (a numpy array or a torch tensor; a device tensor
+    is passed by pointer): (d2, idx, count, mean, device_ms, info) -- torch tensors on the device, d2 float32 (n, k) and
+    idx int32 (n, k), ascending in (d2, idx) with (+inf, -1) in the empty slots, count int32 (n,) holding the uint32 m's
+    bits, mean float32 (n,), each None where its switch is False; info dict(complete, short, not_finite, grid, cells_x,
+    cells_y, cells_z)."""
+    torch, lib, d, dev, held = _open("a cloud's nearest neighbours", abi.KnnDesc, device_id)
+    d.points, d.n_points = _device_cloud(points, dev, held)
+    d.radius, d.k, d.grid = float(radius), int(k), int(grid)
+    rows = (d.n_points, max(d.k, 0))
+    outs = (torch.empty(rows, dtype=torch.float32, device=dev) if d2 else None,
+            torch.empty(rows, dtype=torch.int32, device=dev) if idx else None,
+            torch.empty(d.n_points, dtype=torch.int32, device=dev) if count else None,
+            torch.empty(d.n_points, dtype=torch.float32, device=dev) if mean else None)
+    info, ms = _call(torch, lib, "gipuma_hip_cloud_knn", d, dev, outs, _KNN_INFO)
+    del info["unused"]
+    return outs + (ms, info)
+
+
+def nearest_k(points, radius, k, grid=0, device_id=0, return_info=False):
+    """For every point of the cloud its (at most) k nearest OTHER finite points within `radius` (inclusive; an exact copy is
+    one): (d2 (n, k) float32, idx (n, k) int32, m (n,) uint32), numpy -- row i ascending in (d2, idx), its
+    first m[i] slots filled, the others (+inf, -1); with return_info also device_ms and dict(complete, short, not_finite,
+    grid, cells_x, cells_y, cells_z)."""
+    d2, idx, m, _, ms, info = knn(points, radius, k, grid, device_id, mean=False)
+    out = d2.cpu().numpy(), idx.cpu().numpy(), m.cpu().numpy().view(np.uint32)
+    return out + (ms, info) if return_info else out
+
+
+def outlier_threshold(mean, std_ratio):
+    """(keep mask, mu, sigma, t) of the statistical filter from the float32 `mean` of gipuma_hip_cloud_knn (+inf: fewer
+    than k neighbours): mu and sigma are the mean and the population standard deviation of the finite entries -- the
+    points with a complete list -- in numpy float64, in index order; t = float32(mu + std_ratio * sigma); a point is kept
+    iff its list is complete and mean <= t.  No complete list: nothing kept, mu = sigma = t = NaN."""
+    mean = np.asarray(mean, dtype=np.float32)
+    complete = np.isfinite(mean)
+    if not complete.any():
+        return np.zeros(len(mean), dtype=bool), float("nan"), float("nan"), float("nan")
+    of = mean[complete].astype(np.float64)
+    mu, sigma = float(of.mean()), float(of.std())
+    with np.errstate(over="ignore"):
+        t = np.float32(mu + float(std_ratio) * sigma)
+    return complete & (mean <= t), mu, sigma, float(t)
+
+
+def drop_outliers(points, radius, k, std_ratio, grid=0, device_id=0, return_info=False):
+    """Drops the statistical outliers of a cloud: with mean(i) the mean distance from point i to its k
+    nearest other finite points within `radius`, and mu, sigma the mean and standard deviation of that figure over the
+    points that have k such neighbours, a point is kept iff it has k neighbours within `radius` and mean(i) <= mu +
+    std_ratio * sigma.  A point with fewer is dropped and takes no part in mu, sigma: this is drop_isolated's rule with
+    min_neighbours = k.  Returns the ascending int64 indices of the kept points (numpy), like `thin`; with return_info also
+    device_ms and dict(complete, short, not_finite, grid, cells_x, cells_y, cells_z, mu, sigma, threshold).  Only the
+    means are asked of the library, where +inf says "fewer than k"; a radius whose float32 square is +inf (above 1.8e19) is
+    refused, because there a complete list may hold an overflowed d2 and say +inf as well."""
+    if not (std_ratio >= 0 and np.isfinite(std_ratio)):
+        raise ValueError("std_ratio must be >= 0 and finite, got %r" % (std_ratio,))
+    with np.errstate(over="ignore"):
+        if np.isposinf(np.float32(radius) * np.float32(radius)):
+            raise ValueError("the filter needs a radius whose float32 square is finite, got %r" % (radius,))
+    _, _, _, mean, ms, info = knn(points, radius, k, grid, device_id, d2=False, idx=False, count=False)
+    keep, mu, sigma, t = outlier_threshold(mean.cpu().numpy(), std_ratio)
+    kept = np.nonzero(keep)[0].astype(np.int64)
+    return (kept, ms, dict(info, mu=mu, sigma=sigma, threshold=t)) if return_info else kept
+
+
 def direction_score(d2, thresholds):
     """One direction of the score from its squared distances (float32, +inf: none): ({mean, median, found, none} over the
     points that found a neighbour, [share of ALL points with d <= tau for tau in thresholds] -- "none" is a miss)."""
@@ -180,7 +252,7 @@ def _reduced(a, radius, seed, device_id):
 
 
 def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device_id=0, reduce=0.0, reduce_reference=False,
-          seed=0, neighbour_radius=0.0, min_neighbours=0, return_indices=False):
+          seed=0, neighbour_radius=0.0, min_neighbours=0, return_indices=False, outlier_radius=0.0, outlier_k=0, outlier_std=0.0):
     """Both directions of the score.  accuracy: {mean, median, found, none} of d = sqrt(d2) (float64, on the host) over
     the cloud's points that found a reference point within max_dist; completeness: the same over the reference's points;
     precision / recall per threshold: the share of ALL cloud / reference points with d <= tau; fscore = 2PR / (P + R), 0
@@ -190,8 +262,11 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
     cloud_points_before, reference_points_before, thin_rounds and thin_device_ms (cloud first, then the reference).
     neighbour_radius > 0: the cloud -- never the reference -- then loses its isolated points (drop_isolated with
     min_neighbours), after the thinning and before both searches; the report then also carries neighbour_radius,
-    min_neighbours, cloud_points_before_filter and filter_device_ms.  return_indices: (report, the ascending indices into
-    `cloud` of the points scored, or None where all were)."""
+    min_neighbours, cloud_points_before_filter and filter_device_ms.  outlier_radius > 0: the cloud -- never the reference
+    -- then loses its statistical outliers (drop_outliers with outlier_k and outlier_std), after both, before both
+    searches; the report then also carries outlier_radius, outlier_k, outlier_std, outlier_threshold,
+    cloud_points_before_outliers and outlier_device_ms.  return_indices: (report, the ascending indices into `cloud` of
+    the points scored, or None where all were)."""
     thresholds = [float(t) for t in thresholds]
     if not (reduce >= 0 and np.isfinite(reduce)):
         raise ValueError("reduce must be >= 0 and finite, got %r" % (reduce,))
@@ -199,6 +274,12 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
         raise ValueError("neighbour_radius must be >= 0 and finite, got %r" % (neighbour_radius,))
     if int(min_neighbours) != min_neighbours or min_neighbours < 0:
         raise ValueError("min_neighbours must be an integer >= 0, got %r" % (min_neighbours,))
+    if not (outlier_radius >= 0 and np.isfinite(outlier_radius)):
+        raise ValueError("outlier_radius must be >= 0 and finite, got %r" % (outlier_radius,))
+    if outlier_radius > 0 and (int(outlier_k) != outlier_k or not 1 <= outlier_k <= 32):
+        raise ValueError("outlier_k must be an integer 1..32, got %r" % (outlier_k,))
+    if outlier_radius > 0 and not (outlier_std >= 0 and np.isfinite(outlier_std)):
+        raise ValueError("outlier_std must be >= 0 and finite, got %r" % (outlier_std,))
     before, thinned, indices = (int(cloud.shape[0]), int(reference.shape[0])), [], None
     if reduce > 0:
         cloud, indices, t = _reduced(cloud, reduce, seed, device_id)
@@ -209,6 +290,11 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
     if neighbour_radius > 0:  # (after the thinning: a count means the same everywhere once the density is normalised)
         before_filter = int(cloud.shape[0])
         kept, filter_ms, _ = drop_isolated(cloud, neighbour_radius, min_neighbours, device_id=device_id, return_info=True)
+        cloud, indices = _taken(cloud, kept, device_id), kept if indices is None else indices[kept]
+    if outlier_radius > 0:  # (after both: the mean distance to k neighbours is a figure of the normalised, cleaned cloud)
+        before_outliers = int(cloud.shape[0])
+        kept, outlier_ms, o_info = drop_outliers(cloud, outlier_radius, int(outlier_k), outlier_std, device_id=device_id,
+                                                 return_info=True)
         cloud, indices = _taken(cloud, kept, device_id), kept if indices is None else indices[kept]
     a_d2, _, a_ms, a_info = nearest(cloud, reference, max_dist, grid, device_id, return_info=True)
     c_d2, _, c_ms, c_info = nearest(reference, cloud, max_dist, grid, device_id, return_info=True)
@@ -222,7 +308,26 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
     if neighbour_radius > 0:
         out.update({"neighbour_radius": float(neighbour_radius), "min_neighbours": int(min_neighbours),
                     "cloud_points_before_filter": before_filter, "filter_device_ms": filter_ms})
+    if outlier_radius > 0:
+        out.update({"outlier_radius": float(outlier_radius), "outlier_k": int(outlier_k), "outlier_std": float(outlier_std),
+                    "outlier_threshold": o_info["threshold"], "cloud_points_before_outliers": before_outliers,
+                    "outlier_device_ms": outlier_ms})
     return (out, indices) if return_indices else out
+
+
+def check_outlier_args(pa, args, radius, k, std):
+    """the three options of the statistical filter (this command's and batch's --fuse_* ones): they need each other, the
+    radius goes through float32; off: radius 0.0, k 0, std 0.0"""
+    r, kk, s = float(np.float32(getattr(args, radius))), getattr(args, k), getattr(args, std)
+    if not (r >= 0 and np.isfinite(r)):
+        pa.error("--%s must be >= 0 and finite (0: off)" % radius)
+    if len({r > 0, kk is not None, s is not None}) != 1:
+        pa.error("--%s, --%s and --%s need each other" % (radius, k, std))
+    if kk is not None and not 1 <= kk <= 32:
+        pa.error("--%s must be 1..32" % k)
+    if s is not None and not (s >= 0 and np.isfinite(s)):
+        pa.error("--%s must be >= 0 and finite" % std)
+    setattr(args, radius, r), setattr(args, k, kk or 0), setattr(args, std, s or 0.0)
 
 
 def parse_args(argv):
@@ -241,8 +346,14 @@ def parse_args(argv):
                     help="with --min_neighbours: after --reduce, drop the cloud's points that have fewer than that many "
                          "other points within this radius (0: off)")
     pa.add_argument("--min_neighbours", type=int, default=None, help="with --neighbour_radius: the count a point needs to stay")
+    pa.add_argument("--outlier_radius", type=float, default=0.0,
+                    help="with --outlier_k and --outlier_std: after --reduce and --neighbour_radius, drop the cloud's points "
+                         "whose mean distance to their k nearest neighbours within this radius is above the cloud's mean of it "
+                         "by more than that many standard deviations, and those with fewer than k neighbours there (0: off)")
+    pa.add_argument("--outlier_k", type=int, default=None, help="with --outlier_radius: the number of nearest neighbours, 1..32")
+    pa.add_argument("--outlier_std", type=float, default=None, help="with --outlier_radius: the standard deviations allowed, >= 0")
     pa.add_argument("--write_cloud", default=None,
-                    help="write the cloud as it is scored, after --reduce and / or --neighbour_radius, as a binary PLY with "
+                    help="write the cloud as it is scored, after --reduce, --neighbour_radius and / or --outlier_radius, as a binary PLY with "
                          "every vertex property of --cloud")
     pa.add_argument("--device", type=int, default=0)
     pa.add_argument("--output", default=None, help="write the report (JSON) here")
@@ -273,6 +384,7 @@ def parse_args(argv):
     if args.min_neighbours is not None and not 0 <= args.min_neighbours < 2 ** 31:
         pa.error("--min_neighbours must be 0 .. 2^31 - 1")
     args.min_neighbours = args.min_neighbours or 0
+    check_outlier_args(pa, args, "outlier_radius", "outlier_k", "outlier_std")
     return args
 
 
@@ -282,7 +394,8 @@ def main(argv=None):
     report, indices = score(dmb.read_ply_xyz(args.cloud), dmb.read_ply_xyz(args.reference), args.max_dist, args.thresholds,
                             grid=args.grid, device_id=args.device, reduce=args.reduce, reduce_reference=args.reduce_reference,
                             seed=args.seed, neighbour_radius=args.neighbour_radius, min_neighbours=args.min_neighbours,
-                            return_indices=True)
+                            return_indices=True, outlier_radius=args.outlier_radius, outlier_k=args.outlier_k,
+                            outlier_std=args.outlier_std)
     report.update({"cloud": args.cloud, "reference": args.reference})
     if args.write_cloud:
         dmb.write_ply_vertices(args.write_cloud, vertices if indices is None else vertices[indices])
@@ -297,14 +410,19 @@ def main(argv=None):
              "/".join("%g" % t for t in args.thresholds), report["accuracy_device_ms"], report["completeness_device_ms"]))
     if args.reduce > 0:
         print("thinned to a spacing of %g first: cloud %d -> %d points, reference %d -> %d, %s rounds, %s ms on device"
-              % (args.reduce, report["cloud_points_before"], report.get("cloud_points_before_filter", report["cloud_points"]),
+              % (args.reduce, report["cloud_points_before"], report.get("cloud_points_before_filter", report.get("cloud_points_before_outliers", report["cloud_points"])),
                  report["reference_points_before"],
                  report["reference_points"], "/".join("%d" % r for r in report["thin_rounds"]),
                  "/".join("%.2f" % m for m in report["thin_device_ms"])))
     if args.neighbour_radius > 0:
         print("points with fewer than %d others within %g dropped: cloud %d -> %d points, %.2f ms on device"
-              % (args.min_neighbours, args.neighbour_radius, report["cloud_points_before_filter"], report["cloud_points"],
-                 report["filter_device_ms"]))
+              % (args.min_neighbours, args.neighbour_radius, report["cloud_points_before_filter"],
+                 report.get("cloud_points_before_outliers", report["cloud_points"]), report["filter_device_ms"]))
+    if args.outlier_radius > 0:
+        print("points with a mean distance above %g to their %d nearest within %g (%g standard deviations) dropped: cloud %d -> %d "
+              "points, %.2f ms on device"
+              % (report["outlier_threshold"], args.outlier_k, args.outlier_radius, args.outlier_std,
+                 report["cloud_points_before_outliers"], report["cloud_points"], report["outlier_device_ms"]))
     return 0
 
 

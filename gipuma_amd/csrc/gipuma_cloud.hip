@@ -25,11 +25,12 @@
 // cell varies from run to run.  The contract's result does not depend on that order: the search carries (d2, j) compared
 // lexicographically, and a cell's points are all visited or all skipped.
 //
-// The same grid has two more clients, on the cloud's own box: thinning it to a minimum point spacing (namespace thin,
-// DESIGN.md 15, gipuma_hip_cloud_thin) and counting each point's neighbours within a radius (namespace support, DESIGN.md
-// 16, gipuma_hip_cloud_neighbours).  What they share is written once in namespace cloud.  Device: d2_of (the contract's
+// The same grid has three more clients, on the cloud's own box: thinning it to a minimum point spacing (namespace thin,
+// DESIGN.md 15, gipuma_hip_cloud_thin), counting each point's neighbours within a radius (namespace support, DESIGN.md
+// 16, gipuma_hip_cloud_neighbours) and listing each point's k nearest neighbours with their mean distance (namespace knn,
+// DESIGN.md 17, gipuma_hip_cloud_knn).  What they share is written once in namespace cloud.  Device: d2_of (the contract's
 // d2, the search's too) and Reach (the cells a lane visits and a row's records, with kReach: why no neighbour is skipped).
-// Host: Box, lay_out and sort_by_cell, which the search takes for its targets, and OwnGrid, which runs them for the two.
+// Host: Box, lay_out and sort_by_cell, which the search takes for its targets, and OwnGrid, which runs them for the three.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -449,7 +450,7 @@ int sort_by_cell(hipStream_t st, const float *pts, uint32_t n, const Layout &l, 
     return 0;
 }
 
-// A cloud sorted on a grid over its OWN box: the host set-up of the thinning and the neighbour count.  The steps are calls of
+// A cloud sorted on a grid over its OWN box: the host set-up of the thinning, the neighbour count and the k-NN lists.  The steps are calls of
 // their own, as Box's are, so that a caller's event and its own memsets keep their places on the stream.
 struct OwnGrid {
     Box box;        // (the caller allocates it, before its first event)
@@ -478,7 +479,7 @@ struct OwnGrid {
     {
         return sort_by_cell<false>(st, pts, n, l, cellid, cells, sorted, nullptr, nullptr, counters, nullptr);
     }
-    // info[8] of both calls: kept, dropped, not finite, the caller's fourth figure, G, cells x, y, z
+    // info[8] of the three calls: kept (knn: complete), dropped (knn: short), not finite, the caller's fourth figure, G, cells x, y, z
     void report(int64_t info[8], uint32_t n, uint32_t finite, uint32_t kept, uint32_t fourth) const
     {
         const int64_t figures[4] = {kept, (int64_t)finite - kept, (int64_t)n - finite, fourth};
@@ -647,6 +648,157 @@ __global__ __launch_bounds__(kBlock) void count_kernel(const Rec *__restrict__ s
 
 }  // namespace support
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The k nearest neighbours of every point inside its own cloud, and their mean distance: statistical outlier removal
+// (restated on the CPU by tests/knn_ref.py).  The contract, defined without any grid: for a finite point i,
+//     N(i)    = { j != i : P_j finite and d2(i, j) <= r2 }          (cloud's d2, the thinning's inclusive radius, j != i by index)
+//     list(i) = the min(k, |N(i)|) smallest pairs (d2(i, j), j) of N(i), lexicographically, ascending;  m(i) = its length
+//     mean(i) = m(i) == k ? (((sqrt(d2_0) + sqrt(d2_1)) + ...) + sqrt(d2_{k-1})) / (float)k : +inf
+// float32, the sum in ascending slot order, every sqrt and the division correctly rounded; a point that is not finite has
+// m = 0, empty slots (+inf, -1) and mean = +inf, and no other point lists it.  The k smallest of a set of distinct pairs,
+// sorted, do not depend on the order the records are visited in.
+//
+// Launches, all on one stream:
+//   cloud::OwnGrid (box_*, count_kernel<false>, scan_kernel, scatter_kernel)   the thinning's set-up
+//   knn::clear_kernel                              (+inf, -1), 0 and +inf everywhere: what a point that is never sorted keeps
+//   knn::topk_kernel<K>, once, K = the smallest of 8 / 16 / 32 that holds k: one lane per sorted position over the cells of
+//                                                  its cloud::Reach (no neighbour is skipped: kReach); the results go to
+//                                                  the caller's index
+// The lane's list is K (d2, j) pairs in NAMED registers: every loop over the slots is fully unrolled, so no slot is indexed
+// at run time and the compiler has no reason to put the list into scratch memory, which the unit does not use.  There is
+// no LDS staging and the walk does not shrink to the current k-th distance: both are unmeasured ideas.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace knn {
+
+using namespace cloud;  // (Rec, Grid, Reach, d2_of, kBlock)
+
+constexpr int kMaxK = 32;
+enum { kComplete = cloud::kStats, kShort, kCounters };  // the device counters, behind cloud's (kTargets: the finite points)
+
+// The unit spells no fused multiply-add (its assembly is tested for that), and the compiler's own correctly rounded sqrtf
+// and `/` are built from them.  So both are written here: the hardware's approximation, then ONE step to the neighbouring
+// float decided by exact arithmetic in double -- a float has 24 significant bits, the midpoint of two adjacent floats 25, and
+// a product of two such numbers at most 50: it is exact in a double's 53, whatever the rounding mode.
+__device__ __forceinline__ float up(float s) { return __uint_as_float(__float_as_uint(s) + 1u); }    // (s > 0, finite, not the largest)
+__device__ __forceinline__ float down(float s) { return __uint_as_float(__float_as_uint(s) - 1u); }  // (s > 0)
+
+// sqrt(x), correctly rounded, for x >= 0 or +inf.  v_sqrt_f32 is good to 1 ulp on normal inputs, so the correctly rounded
+// root is s or one of its two neighbours: it is the float whose interval between the midpoints to its neighbours holds the
+// real root, i.e. lo^2 < x < hi^2.  (A midpoint's square has an odd 50th bit: it is no float, and equality cannot occur.)
+// An x below 2^-96 (subnormals among them, which the instruction does not take) is scaled by 2^64, its root by 2^-32, both
+// exactly: the root of the smallest subnormal is 2^-74.5.
+__device__ __forceinline__ float root(float x)
+{
+    if (!(x > 0.f) || x == INFINITY) return x;  // 0 and +inf are their own roots
+    const bool tiny = x < 0x1p-96f;
+    const float xs = tiny ? x * 0x1p64f : x;
+    float s = __builtin_amdgcn_sqrtf(xs);
+#pragma unroll
+    for (int step = 0; step < 2; ++step) {  // (one step is what 1 ulp needs; the second costs a compare and asks nothing of it)
+        const double hi = 0.5 * ((double)s + (double)up(s)), lo = 0.5 * ((double)s + (double)down(s));
+        if ((double)xs > hi * hi) s = up(s);
+        else if ((double)xs < lo * lo) s = down(s);
+    }
+    return tiny ? s * 0x1p-32f : s;
+}
+
+// a / k, correctly rounded, for a >= 0 or +inf and an integer 1 <= k <= 32 (inv_k = 1.0 / k in double, from the host).
+// The double product is within 2^-52 of the quotient, so its rounding to float is the answer or its neighbour on the side
+// of a midpoint; q is right iff lo * k <= a <= hi * k for the two midpoints, products of 25 and 6 bits, exact.  a is 0 or at
+// least 2^-75 here (a sum of roots), so q is normal, and a normal quotient by an integer below 2^24 is never a midpoint.
+__device__ __forceinline__ float quotient(float a, float k, double inv_k)
+{
+    if (!(a > 0.f) || a == INFINITY) return a;
+    float q = (float)((double)a * inv_k);
+    const double hi = 0.5 * ((double)q + (double)up(q)), lo = 0.5 * ((double)q + (double)down(q));
+    if ((double)a > hi * (double)k) q = up(q);
+    else if ((double)a < lo * (double)k) q = down(q);
+    return q;
+}
+
+// what a point that is never sorted keeps: empty slots, m = 0, mean = +inf (each where the caller asked for the output)
+__global__ __launch_bounds__(kBlock) void clear_kernel(uint32_t n, uint32_t slots, float *__restrict__ out_d2, int32_t *__restrict__ out_idx,
+                                                       uint32_t *__restrict__ out_m, float *__restrict__ out_mean)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // (slots = n * k < 2^31)
+    if (i < slots) {
+        if (out_d2) out_d2[i] = INFINITY;
+        if (out_idx) out_idx[i] = -1;
+    }
+    if (i < n) {
+        if (out_m) out_m[i] = 0u;
+        if (out_mean) out_mean[i] = INFINITY;
+    }
+}
+
+// *n_sorted: the number of sorted (finite) points, as the histogram left it on the device.  The list is ascending in
+// (d2, j); an empty slot is (+inf, -1) and indices compare UNSIGNED, so that -1 loses to every real index: where r2 = +inf
+// a neighbour whose d2 overflowed to +inf (inf <= inf) displaces an empty slot and ties are still decided by the index.
+// A record that passes the gate is below the last slot; it is carried down the list: each slot keeps the smaller of itself
+// and the carry and hands the larger on, and what falls out of slot K - 1 is the old last pair.
+template <int K>
+__global__ __launch_bounds__(kBlock) void topk_kernel(const Rec *__restrict__ sorted, const uint32_t *__restrict__ ends,
+                                                      const uint32_t *__restrict__ n_sorted, Grid g, float reach, int k, double inv_k,
+                                                      float *__restrict__ out_d2, int32_t *__restrict__ out_idx,
+                                                      uint32_t *__restrict__ out_m, float *__restrict__ out_mean,
+                                                      uint32_t *__restrict__ counters)
+{
+    const uint32_t pos = blockIdx.x * kBlock + threadIdx.x;
+    bool complete = false, is_short = false;
+    if (pos < *n_sorted) {
+        const Rec a = sorted[pos];
+        const Reach r(a, reach, g);
+        float d[K];
+        uint32_t j[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) d[s] = INFINITY, j[s] = ~0u;
+        for (int z = r.z0; z <= r.z1; ++z)
+            for (int y = r.y0; y <= r.y1; ++y) {
+                uint32_t p, end;
+                for (r.row(ends, g, y, z, p, end); p < end; ++p) {
+                    const Rec b = sorted[p];
+                    float cd = d2_of(a, b);
+                    uint32_t cj = (uint32_t)b.j;
+                    if (!(cd <= g.r2) || p == pos || !(cd < d[K - 1] || (cd == d[K - 1] && cj < j[K - 1]))) continue;
+#pragma unroll
+                    for (int s = 0; s < K; ++s) {
+                        const bool below = cd < d[s] || (cd == d[s] && cj < j[s]);
+                        const float td = d[s];
+                        const uint32_t tj = j[s];
+                        d[s] = below ? cd : td;
+                        j[s] = below ? cj : tj;
+                        cd = below ? td : cd;
+                        cj = below ? tj : cj;
+                    }
+                }
+            }
+        // the outputs: slots k .. K - 1 are never written out; m counts the filled ones of the first k
+        uint32_t m = 0;
+        float sum = 0.f;
+        const size_t base = (size_t)a.j * (size_t)k;
+#pragma unroll
+        for (int s = 0; s < K; ++s)
+            if (s < k) {
+                m += j[s] != ~0u;
+                sum = sum + root(d[s]);
+                if (out_d2) out_d2[base + s] = d[s];
+                if (out_idx) out_idx[base + s] = (int32_t)j[s];
+            }
+        complete = m == (uint32_t)k;
+        is_short = !complete;
+        if (out_m) out_m[a.j] = m;
+        if (out_mean) out_mean[a.j] = complete ? quotient(sum, (float)k, inv_k) : INFINITY;
+    }
+    // the counters: one atomic each per wavefront (integer sums: the totals do not depend on the order)
+    const uint64_t bc = __ballot(complete), bs = __ballot(is_short);
+    if ((threadIdx.x & 63) == 0) {
+        if (bc) atomicAdd(&counters[kComplete], (uint32_t)__popcll(bc));
+        if (bs) atomicAdd(&counters[kShort], (uint32_t)__popcll(bs));
+    }
+}
+
+}  // namespace knn
+
 namespace {
 
 thread_local int64_t last_stats[6] = {0, 0, 0, 0, 0, 0};  // gipuma_hip_cloud_last_stats
@@ -811,17 +963,56 @@ int run_neighbours(const gipuma_hip_neighbours_desc *d, uint32_t *count_dev, uin
     return 0;
 }
 
-// The checks the three entry points share, in their order, `what` before every text.  null_pointer: the entry point's own
-// rule; own: the text of the first of its own checks that fails (null: none), reported in its place.  The device comes last.
+int run_knn(const gipuma_hip_knn_desc *d, float *d2_dev, int32_t *idx_dev, uint32_t *count_dev, float *mean_dev, int64_t info[8],
+            float *device_ms)
+{
+    const uint32_t n = (uint32_t)d->n_points, k = (uint32_t)d->k;
+    HIP_OK(hipSetDevice(d->device_id));
+    pm_host::CallScope sc;
+    if (const int rc = sc.open(d->stream, 2)) return rc;
+    hipStream_t st = sc.st;
+    cloud::OwnGrid og;
+    uint32_t counters[knn::kCounters] = {};
+    float ms = 0.f;
+
+    if (n) {
+        // every output comes out of the kernel with the finite points' entries written over the clearing
+        if (const int rc = og.box.alloc(sc, n)) return rc;
+        HIP_OK(hipEventRecord(sc.e[0], st));
+        hipLaunchKernelGGL(knn::clear_kernel, cloud::blocks_for(d2_dev || idx_dev ? n * k : n), dim3(cloud::kBlock), 0, st, n, n * k,
+                           d2_dev, idx_dev, count_dev, mean_dev);
+        HIP_OK(hipGetLastError());
+        if (const int rc = og.lay(sc, d->points, n, d->radius, d->grid, knn::kCounters)) return rc;
+        if (og.any) {  // (else: no point has a list)
+            if (const int rc = og.sort(st, d->points, n)) return rc;
+            const auto kernel = k <= 8 ? knn::topk_kernel<8> : k <= 16 ? knn::topk_kernel<16> : knn::topk_kernel<knn::kMaxK>;
+            hipLaunchKernelGGL(kernel, cloud::blocks_for(n), dim3(cloud::kBlock), 0, st, og.sorted, og.cells, og.counters + cloud::kTargets,
+                               og.l.g, cloud::kReach * d->radius, (int)k, 1.0 / (double)k, d2_dev, idx_dev, count_dev, mean_dev,
+                               og.counters);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipMemcpyAsync(counters, og.counters, sizeof counters, hipMemcpyDeviceToHost, st));
+        }
+        HIP_OK(hipEventRecord(sc.e[1], st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(&ms, sc.e[0], sc.e[1]));
+    }
+    og.report(info, n, counters[cloud::kTargets], counters[knn::kComplete], 0);
+    if (device_ms) *device_ms = ms;
+    return 0;
+}
+
+// The checks the four entry points share, in their order, `what` before every text.  null_pointer: the entry point's own
+// rule; own: the text of the first of its own checks that fails (null: none), reported in its place with own_rc.  The device
+// comes last.
 int check_args(const char *what, int abi_version, int64_t n0, int64_t n1, bool null_pointer, const char *dist_name, float dist,
-               const char *own, int grid, int device_id)
+               const char *own, int grid, int device_id, int own_rc = GIPUMA_HIP_ERR_ARG)
 {
     if (abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "%s: abi_version mismatch", what);
     if (n0 < 0 || n1 < 0) return fail(GIPUMA_HIP_ERR_ARG, "%s: negative point count", what);
     if ((n0 | n1) >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "%s: a cloud may hold at most 2^31 - 1 points", what);
     if (null_pointer) return fail(GIPUMA_HIP_ERR_ARG, "%s: null pointer with a non-zero point count", what);
     if (!(dist > 0.f) || !std::isfinite(dist)) return fail(GIPUMA_HIP_ERR_ARG, "%s: %s must be > 0 and finite", what, dist_name);
-    if (own) return fail(GIPUMA_HIP_ERR_ARG, "%s: %s", what, own);
+    if (own) return fail(own_rc, "%s: %s", what, own);
     if (grid < 0 || grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "%s: grid must be 0 (automatic) or 1..256", what);
     return pm_host::check_device(device_id);
 }
@@ -869,6 +1060,20 @@ int gipuma_hip_cloud_neighbours(const gipuma_hip_neighbours_desc *d, uint32_t *c
                                   "radius", d->radius, own, d->grid, d->device_id))
         return rc;
     return run_neighbours(d, count_dev, keep_dev, info, device_ms);
+}
+
+int gipuma_hip_cloud_knn(const gipuma_hip_knn_desc *d, float *d2_dev, int32_t *idx_dev, uint32_t *count_dev, float *mean_dev,
+                         int64_t info[8], float *device_ms)
+{
+    if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
+    const bool bad_k = d->k < 1 || d->k > knn::kMaxK;
+    const bool too_many = !bad_k && (d2_dev || idx_dev) && d->n_points >= ((1ll << 31) + d->k - 1) / d->k;  // n * k >= 2^31
+    const char *own = bad_k ? "k must be 1..32" : too_many ? "the lists may hold at most 2^31 - 1 slots (n_points * k)" : nullptr;
+    if (const int rc = check_args("knn", d->abi_version, d->n_points, 0,
+                                  d->n_points && (!d->points || (!d2_dev && !idx_dev && !count_dev && !mean_dev)), "radius", d->radius,
+                                  own, d->grid, d->device_id, bad_k ? GIPUMA_HIP_ERR_ARG : GIPUMA_HIP_ERR_UNSUPPORTED))
+        return rc;
+    return run_knn(d, d2_dev, idx_dev, count_dev, mean_dev, info, device_ms);
 }
 
 }  // extern "C"

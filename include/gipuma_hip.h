@@ -474,6 +474,46 @@ typedef struct gipuma_hip_neighbours_desc {
 int gipuma_hip_cloud_neighbours(const gipuma_hip_neighbours_desc *desc, uint32_t *count_dev, uint8_t *keep_dev,
                                 int64_t info[8], float *device_ms);
 
+/* ---- the k nearest neighbours of every point inside its own cloud, and their mean distance: statistical outlier removal
+ *  ----
+ * P: n_points packed float32 xyz.  d2(i, j) and r2 = radius * radius are the thinning's, float32 without contraction; the
+ * neighbour relation is the neighbour count's: plain d2 <= r2, inclusive, j != i by index, so an exact copy is a neighbour.
+ *     P_i not finite in all three coordinates:  m(i) = 0, every slot (+inf, -1), mean(i) = +inf -- and no point lists i
+ *     otherwise:  N(i)    = { j != i : P_j finite and d2(i, j) <= r2 }
+ *                 list(i) = the min(k, |N(i)|) smallest pairs (d2(i, j), j) of N(i) in lexicographic order, ascending
+ *                 m(i)    = min(k, |N(i)|)
+ *                 d2_dev[i*k + s], idx_dev[i*k + s] = list(i)[s] for s < m(i);  (+inf, -1) for m(i) <= s < k
+ *                 count_dev[i] = m(i)
+ *                 mean_dev[i]  = m(i) == k ? (((sqrt(d2_0) + sqrt(d2_1)) + ...) + sqrt(d2_{k-1})) / (float)k : +inf
+ * The sum is float32, in ascending slot order, starting from 0; every sqrt and the division are correctly rounded float32
+ * (what numpy's float32 sqrt, + and / do).  The k smallest of a set of distinct pairs, sorted, do not depend on the order
+ * the kernel visits the points in or on the grid: all four outputs equal a brute force in every bit, run after run
+ * (tests/knn_ref.py).  m(i) == k is the neighbour count's keep(i) with min_neighbours = k.
+ * Where r2 = +inf (radius above 1.8e19) inf <= inf holds, as in the thinning: a finite P_j whose d2 overflows is a neighbour.
+ * A slot with d2 = +inf and idx >= 0 is such a neighbour -- it is filled, it counts in m(i), it sorts behind every finite d2
+ * by its index, and a list that holds one has mean = +inf although m(i) == k.  An EMPTY slot is the one with idx = -1.
+ * `grid` is the thinning's and changes the time only.  n_points = 0 writes nothing.  Blocks until the outputs are
+ * complete; the cloud must be complete on desc->stream's terms when the call is made.  Scratch (about 20 bytes per point
+ * and 4 per cell) is allocated for the call and freed before it returns, on every error path too. */
+typedef struct gipuma_hip_knn_desc {
+    uint32_t abi_version; /* GIPUMA_HIP_ABI_VERSION */
+    int64_t n_points;     /* < 2^31; more: GIPUMA_HIP_ERR_UNSUPPORTED */
+    const float *points;  /* device pointer, packed xyz float32 */
+    float radius;         /* > 0 and finite, else GIPUMA_HIP_ERR_ARG */
+    int32_t k;            /* 1..32, else GIPUMA_HIP_ERR_ARG */
+    int32_t grid;         /* 0: automatic; 1..256: cells along the longest axis */
+    int32_t device_id;    /* HIP device ordinal */
+    void *stream;         /* hipStream_t to launch on, NULL = one the library creates for the call */
+} gipuma_hip_knn_desc;
+
+/* d2_dev, idx_dev: n_points * k entries each, device; count_dev (uint32), mean_dev: n_points entries each, device.  Each may
+ * be NULL, not all four where n_points > 0 (GIPUMA_HIP_ERR_ARG); with d2_dev or idx_dev given, n_points * k must be below
+ * 2^31 (GIPUMA_HIP_ERR_UNSUPPORTED).  info (points with a complete list, m == k; finite points with a short one; points not
+ * finite; 0; cells along the longest axis, cells along x, y and z) and device_ms (HIP events around everything the call
+ * enqueues) may be NULL. */
+int gipuma_hip_cloud_knn(const gipuma_hip_knn_desc *desc, float *d2_dev, int32_t *idx_dev, uint32_t *count_dev,
+                         float *mean_dev, int64_t info[8], float *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
