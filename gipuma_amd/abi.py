@@ -150,6 +150,15 @@ class NeighboursDesc(C.Structure):
     ]
 
 
+class ComponentsDesc(C.Structure):
+    """gipuma_hip_components_desc: one device cloud of packed float32 xyz, the radius of the edge relation, the size a
+    component needs for its points to be kept and the grid (0: automatic)"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("n_points", C.c_int64), ("points", C.c_void_p), ("radius", C.c_float),
+        ("min_size", C.c_int32), ("grid", C.c_int32), ("device_id", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
 class KnnDesc(C.Structure):
     """gipuma_hip_knn_desc: one device cloud of packed float32 xyz, the radius, the list length k (1..32) and the grid (0:
     automatic)"""
@@ -198,6 +207,8 @@ SYMBOLS = [
     ("gipuma_hip_cloud_neighbours", C.c_int, [C.POINTER(NeighboursDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), _FP]),
     ("gipuma_hip_cloud_knn", C.c_int, [C.POINTER(KnnDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
                                        _FP]),
+    ("gipuma_hip_cloud_components", C.c_int, [C.POINTER(ComponentsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+                                              _FP]),
 ]
 
 _lib = None

@@ -41,7 +41,11 @@ MI355X-first differences from the shell loop:
   * --fuse_outlier_radius r --fuse_outlier_k K --fuse_outlier_std s (with --fuse): the fused cloud then loses its
     statistical outliers -- the points whose mean distance to their K nearest neighbours within r exceeds the cloud's
     mean of that figure by more than s standard deviations, and those with fewer than K neighbours there (DESIGN.md 17,
-    gipuma_amd.cloud_eval.drop_outliers) -- after --fuse_neighbour_radius, before fused.ply is written and scored.
+    gipuma_amd.cloud_eval.drop_outliers) -- after --fuse_neighbour_radius, before fused.ply is written and scored;
+  * --fuse_component_radius r --fuse_min_component N (with --fuse): the fused cloud then loses its small clumps -- every
+    connected component of its radius graph (points joined where they lie within r of each other) with fewer than N
+    points (gipuma_amd.cloud_eval.drop_small_components) -- after --fuse_outlier_radius, before fused.ply
+    is written and scored.
 
 Images: what the reference's scripts hand to imread (main.cpp:739-751) -- PNG, JPG (through PIL), binary PGM / PPM.
 Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
@@ -343,6 +347,12 @@ def parse_args(argv):
     pa.add_argument("--fuse_outlier_k", type=int, default=None, help="with --fuse_outlier_radius: the number of nearest neighbours, 1..32")
     pa.add_argument("--fuse_outlier_std", type=float, default=None,
                     help="with --fuse_outlier_radius: the standard deviations allowed, >= 0")
+    pa.add_argument("--fuse_component_radius", type=float, default=0.0,
+                    help="with --fuse and --fuse_min_component: after --fuse_outlier_radius, drop the fused points whose "
+                         "connected component -- points joined where they lie within this radius of each other -- has fewer "
+                         "than that many points (0: off; DESIGN.md 18)")
+    pa.add_argument("--fuse_min_component", type=int, default=None,
+                    help="with --fuse_component_radius: the points a component needs for them to stay")
     args = pa.parse_args(argv)
     # the reference parses these with sscanf("%f") into float fields (main.cpp:300-360)
     for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
@@ -369,6 +379,10 @@ def parse_args(argv):
     check_outlier_args(pa, args, "fuse_outlier_radius", "fuse_outlier_k", "fuse_outlier_std")
     if args.fuse_outlier_radius > 0 and not args.fuse:
         pa.error("--fuse_outlier_radius filters the fused cloud: it needs --fuse")
+    from .cloud_eval import check_component_args
+    check_component_args(pa, args, "fuse_component_radius", "fuse_min_component")
+    if args.fuse_component_radius > 0 and not args.fuse:
+        pa.error("--fuse_component_radius filters the fused cloud: it needs --fuse")
     if args.levels < 1:
         raise SystemExit("--levels must be >= 1")
     args.level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
@@ -416,6 +430,13 @@ def fuse_solved(scan):
                                                args.fuse_outlier_k, args.fuse_outlier_std, device_id=scan.dev[0].device.index,
                                                return_info=True)
         filtered.update({"points_before_outliers": int(len(points)), "outlier_threshold": o["threshold"], "outlier_device_ms": ms})
+        points = points[kept]
+    if args.fuse_component_radius > 0:  # (then the small clumps, which neither of the two can see)
+        from . import cloud_eval
+        kept, ms, c = cloud_eval.drop_small_components(np.stack([points["x"], points["y"], points["z"]], axis=-1),
+                                                       args.fuse_component_radius, args.fuse_min_component,
+                                                       device_id=scan.dev[0].device.index, return_info=True)
+        filtered.update({"points_before_components": int(len(points)), "components": c["components"], "component_device_ms": ms})
         points = points[kept]
     dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
     scan.fused_xyz = np.stack([points["x"], points["y"], points["z"]], axis=-1)  # (for --eval_cloud)

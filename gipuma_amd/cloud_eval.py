@@ -1,10 +1,10 @@
 """Score a point cloud against a reference cloud on the GPU: accuracy and completeness, after thinning
-the cloud to a minimum point spacing, dropping its isolated points and dropping its
-statistical outliers when asked to.
+the cloud to a minimum point spacing, dropping its isolated points, dropping its
+statistical outliers and dropping its small clumps when asked to.
 
     python -m gipuma_amd.cloud_eval --cloud fused.ply --reference gt.ply --max_dist 20 --thresholds 0.5,1,2 \\
         [--reduce 0.2 [--reduce_reference] [--seed N]] [--neighbour_radius 1 --min_neighbours 8] \\
-        [--outlier_radius 1 --outlier_k 16 --outlier_std 2] \\
+        [--outlier_radius 1 --outlier_k 16 --outlier_std 2] [--component_radius 1 --min_component 100] \\
         [--write_cloud scored.ply] [--output report.json]
 
 DTU -- the data set this project is calibrated on -- scores a reconstruction cloud against cloud: accuracy is the distance
@@ -21,8 +21,12 @@ after the thinning: a count means the same everywhere only once the density is n
 halo a few spacings off a surface, or the smeared rim of a depth step: such points have neighbours enough, only farther away
 than a surface point's.  --outlier_radius / --outlier_k / --outlier_std drop every point whose mean distance to its k
 nearest neighbours within the radius (gipuma_hip_cloud_knn; `knn`, `nearest_k`, `drop_outliers`) exceeds the cloud's mean of
-that figure by more than outlier_std standard deviations, and every point with fewer than k neighbours there.  --write_cloud
-writes the cloud as it is scored.  Not part of the score here: DTU's observability masks and ground-plane removal.
+that figure by more than outlier_std standard deviations, and every point with fewer than k neighbours there.  Neither
+filter sees a CLUMP: forty points fused at a wrong depth have thirty-nine neighbours each, closer than a surface point's.
+--component_radius / --min_component drop every connected component of the radius graph -- points joined where they lie
+within the radius of each other -- that has fewer than min_component points (gipuma_hip_cloud_components,
+gipuma_amd/csrc/gipuma_components.hip; `components`, `component_labels`, `drop_small_components`), after the three;
+`component_labels` also segments a cloud into its objects.  --write_cloud writes the cloud as it is scored.  Not part of the score here: DTU's observability masks and ground-plane removal.
 """
 import argparse
 import ctypes as C
@@ -38,6 +42,7 @@ _STATS = ("grid", "cells_x", "cells_y", "cells_z", "early_out", "searched")
 ORDERS = {"hashed": 0, "index": 1}
 _THIN_INFO = ("kept", "dropped", "not_finite", "rounds", "grid", "cells_x", "cells_y", "cells_z")
 _KNN_INFO = ("complete", "short", "not_finite", "unused", "grid", "cells_x", "cells_y", "cells_z")
+_COMPONENT_INFO = ("kept", "dropped", "not_finite", "components", "grid", "cells_x", "cells_y", "cells_z")
 _NEIGHBOUR_INFO = ("kept", "dropped", "not_finite", "saturated", "grid", "cells_x", "cells_y", "cells_z")
 
 
@@ -219,6 +224,43 @@ def drop_outliers(points, radius, k, std_ratio, grid=0, device_id=0, return_info
     return (kept, ms, dict(info, mu=mu, sigma=sigma, threshold=t)) if return_info else kept
 
 
+def components(points, radius, min_size=0, grid=0, device_id=0, label=True, size=True, keep=True):
+    """The contract of gipuma_hip_cloud_components on the (n, 3) cloud `points` (a numpy array or a torch tensor; a device
+    tensor is passed by pointer): (label, size, keep, device_ms, info) -- label a torch int32 tensor on the device (the
+    smallest index of the point's connected component in the radius graph, -1 for a point that is not finite), size a torch
+    int32 tensor holding the uint32 cardinalities' bits, keep a torch uint8 tensor (size >= min_size), one entry per point
+    each, or None where its switch is False; info dict(kept, dropped, not_finite, components, grid, cells_x, cells_y,
+    cells_z)."""
+    torch, lib, d, dev, held = _open("a cloud's connected components", abi.ComponentsDesc, device_id)
+    d.points, d.n_points = _device_cloud(points, dev, held)
+    d.radius, d.min_size, d.grid = float(radius), int(min_size), int(grid)
+    outs = (torch.empty(d.n_points, dtype=torch.int32, device=dev) if label else None,
+            torch.empty(d.n_points, dtype=torch.int32, device=dev) if size else None,
+            torch.empty(d.n_points, dtype=torch.uint8, device=dev) if keep else None)
+    info, ms = _call(torch, lib, "gipuma_hip_cloud_components", d, dev, outs, _COMPONENT_INFO)
+    return outs + (ms, info)
+
+
+def component_labels(points, radius, grid=0, device_id=0, return_info=False):
+    """The connected components of the cloud's radius graph: two finite points are joined where they lie
+    within `radius` of each other (inclusive; an exact copy is joined).  Returns (label int32, size uint32), numpy: the
+    smallest index of the point's component and the component's number of points, (-1, 0) for a point that is not finite;
+    with return_info also device_ms and dict(kept, dropped, not_finite, components, grid, cells_x, cells_y, cells_z) --
+    min_size is 0 here, so every finite point is `kept`."""
+    label, size, _, ms, info = components(points, radius, 0, grid, device_id, keep=False)
+    out = label.cpu().numpy(), size.cpu().numpy().view(np.uint32)
+    return out + (ms, info) if return_info else out
+
+
+def drop_small_components(points, radius, min_size, grid=0, device_id=0, return_info=False):
+    """Drops the small clumps of a cloud: a point is kept iff it is finite and its connected component in
+    the radius graph has at least `min_size` points.  Returns the ascending int64 indices of the kept points (numpy), like
+    `thin`; with return_info also device_ms and dict(kept, dropped, not_finite, components, grid, cells_x, cells_y,
+    cells_z) -- components counts all of them, the dropped ones too."""
+    _, _, keep, ms, info = components(points, radius, min_size, grid, device_id, label=False, size=False)
+    return (_indices(keep), ms, info) if return_info else _indices(keep)
+
+
 def direction_score(d2, thresholds):
     """One direction of the score from its squared distances (float32, +inf: none): ({mean, median, found, none} over the
     points that found a neighbour, [share of ALL points with d <= tau for tau in thresholds] -- "none" is a miss)."""
@@ -252,7 +294,8 @@ def _reduced(a, radius, seed, device_id):
 
 
 def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device_id=0, reduce=0.0, reduce_reference=False,
-          seed=0, neighbour_radius=0.0, min_neighbours=0, return_indices=False, outlier_radius=0.0, outlier_k=0, outlier_std=0.0):
+          seed=0, neighbour_radius=0.0, min_neighbours=0, return_indices=False, outlier_radius=0.0, outlier_k=0, outlier_std=0.0,
+          component_radius=0.0, min_component=0):
     """Both directions of the score.  accuracy: {mean, median, found, none} of d = sqrt(d2) (float64, on the host) over
     the cloud's points that found a reference point within max_dist; completeness: the same over the reference's points;
     precision / recall per threshold: the share of ALL cloud / reference points with d <= tau; fscore = 2PR / (P + R), 0
@@ -265,7 +308,10 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
     min_neighbours, cloud_points_before_filter and filter_device_ms.  outlier_radius > 0: the cloud -- never the reference
     -- then loses its statistical outliers (drop_outliers with outlier_k and outlier_std), after both, before both
     searches; the report then also carries outlier_radius, outlier_k, outlier_std, outlier_threshold,
-    cloud_points_before_outliers and outlier_device_ms.  return_indices: (report, the ascending indices into `cloud` of
+    cloud_points_before_outliers and outlier_device_ms.  component_radius > 0: the cloud -- never the reference -- then
+    loses its small clumps (drop_small_components with min_component), after the three, before both searches; the report
+    then also carries component_radius, min_component, components, cloud_points_before_components and
+    component_device_ms.  return_indices: (report, the ascending indices into `cloud` of
     the points scored, or None where all were)."""
     thresholds = [float(t) for t in thresholds]
     if not (reduce >= 0 and np.isfinite(reduce)):
@@ -280,6 +326,10 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
         raise ValueError("outlier_k must be an integer 1..32, got %r" % (outlier_k,))
     if outlier_radius > 0 and not (outlier_std >= 0 and np.isfinite(outlier_std)):
         raise ValueError("outlier_std must be >= 0 and finite, got %r" % (outlier_std,))
+    if not (component_radius >= 0 and np.isfinite(component_radius)):
+        raise ValueError("component_radius must be >= 0 and finite, got %r" % (component_radius,))
+    if int(min_component) != min_component or not 0 <= min_component < 2 ** 31:
+        raise ValueError("min_component must be an integer 0 .. 2^31 - 1, got %r" % (min_component,))
     before, thinned, indices = (int(cloud.shape[0]), int(reference.shape[0])), [], None
     if reduce > 0:
         cloud, indices, t = _reduced(cloud, reduce, seed, device_id)
@@ -295,6 +345,11 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
         before_outliers = int(cloud.shape[0])
         kept, outlier_ms, o_info = drop_outliers(cloud, outlier_radius, int(outlier_k), outlier_std, device_id=device_id,
                                                  return_info=True)
+        cloud, indices = _taken(cloud, kept, device_id), kept if indices is None else indices[kept]
+    if component_radius > 0:  # (last: the clumps that are left when single points and loose halos have gone)
+        before_components = int(cloud.shape[0])
+        kept, component_ms, comp_info = drop_small_components(cloud, component_radius, int(min_component), device_id=device_id,
+                                                           return_info=True)
         cloud, indices = _taken(cloud, kept, device_id), kept if indices is None else indices[kept]
     a_d2, _, a_ms, a_info = nearest(cloud, reference, max_dist, grid, device_id, return_info=True)
     c_d2, _, c_ms, c_info = nearest(reference, cloud, max_dist, grid, device_id, return_info=True)
@@ -312,6 +367,10 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
         out.update({"outlier_radius": float(outlier_radius), "outlier_k": int(outlier_k), "outlier_std": float(outlier_std),
                     "outlier_threshold": o_info["threshold"], "cloud_points_before_outliers": before_outliers,
                     "outlier_device_ms": outlier_ms})
+    if component_radius > 0:
+        out.update({"component_radius": float(component_radius), "min_component": int(min_component),
+                    "components": comp_info["components"], "cloud_points_before_components": before_components,
+                    "component_device_ms": component_ms})
     return (out, indices) if return_indices else out
 
 
@@ -328,6 +387,19 @@ def check_outlier_args(pa, args, radius, k, std):
     if s is not None and not (s >= 0 and np.isfinite(s)):
         pa.error("--%s must be >= 0 and finite" % std)
     setattr(args, radius, r), setattr(args, k, kk or 0), setattr(args, std, s or 0.0)
+
+
+def check_component_args(pa, args, radius, size):
+    """the two options of the component filter (this command's and batch's --fuse_* ones): they need each other, the
+    radius goes through float32; off: radius 0.0, size 0"""
+    r, n = float(np.float32(getattr(args, radius))), getattr(args, size)
+    if not (r >= 0 and np.isfinite(r)):
+        pa.error("--%s must be >= 0 and finite (0: off)" % radius)
+    if (r > 0) != (n is not None):
+        pa.error("--%s and --%s need each other" % (radius, size))
+    if n is not None and not 0 <= n < 2 ** 31:
+        pa.error("--%s must be 0 .. 2^31 - 1" % size)
+    setattr(args, radius, r), setattr(args, size, n or 0)
 
 
 def parse_args(argv):
@@ -352,8 +424,15 @@ def parse_args(argv):
                          "by more than that many standard deviations, and those with fewer than k neighbours there (0: off)")
     pa.add_argument("--outlier_k", type=int, default=None, help="with --outlier_radius: the number of nearest neighbours, 1..32")
     pa.add_argument("--outlier_std", type=float, default=None, help="with --outlier_radius: the standard deviations allowed, >= 0")
+    pa.add_argument("--component_radius", type=float, default=0.0,
+                    help="with --min_component: after --reduce, --neighbour_radius and --outlier_radius, drop the cloud's "
+                         "points whose connected component -- points joined where they lie within this radius of each other "
+                         "-- has fewer than that many points (0: off)")
+    pa.add_argument("--min_component", type=int, default=None,
+                    help="with --component_radius: the points a component needs for them to stay")
     pa.add_argument("--write_cloud", default=None,
-                    help="write the cloud as it is scored, after --reduce, --neighbour_radius and / or --outlier_radius, as a binary PLY with "
+                    help="write the cloud as it is scored, after --reduce, --neighbour_radius, --outlier_radius and / or "
+                         "--component_radius, as a binary PLY with "
                          "every vertex property of --cloud")
     pa.add_argument("--device", type=int, default=0)
     pa.add_argument("--output", default=None, help="write the report (JSON) here")
@@ -385,6 +464,7 @@ def parse_args(argv):
         pa.error("--min_neighbours must be 0 .. 2^31 - 1")
     args.min_neighbours = args.min_neighbours or 0
     check_outlier_args(pa, args, "outlier_radius", "outlier_k", "outlier_std")
+    check_component_args(pa, args, "component_radius", "min_component")
     return args
 
 
@@ -395,7 +475,8 @@ def main(argv=None):
                             grid=args.grid, device_id=args.device, reduce=args.reduce, reduce_reference=args.reduce_reference,
                             seed=args.seed, neighbour_radius=args.neighbour_radius, min_neighbours=args.min_neighbours,
                             return_indices=True, outlier_radius=args.outlier_radius, outlier_k=args.outlier_k,
-                            outlier_std=args.outlier_std)
+                            outlier_std=args.outlier_std, component_radius=args.component_radius,
+                            min_component=args.min_component)
     report.update({"cloud": args.cloud, "reference": args.reference})
     if args.write_cloud:
         dmb.write_ply_vertices(args.write_cloud, vertices if indices is None else vertices[indices])
@@ -408,21 +489,27 @@ def main(argv=None):
              report["completeness"]["mean"], report["completeness"]["median"], report["completeness"]["found"],
              report["reference_points"], "/".join("%.4f" % f for f in report["fscore"]),
              "/".join("%g" % t for t in args.thresholds), report["accuracy_device_ms"], report["completeness_device_ms"]))
+    after_outliers = report.get("cloud_points_before_components", report["cloud_points"])  # (what the earlier stages left)
     if args.reduce > 0:
         print("thinned to a spacing of %g first: cloud %d -> %d points, reference %d -> %d, %s rounds, %s ms on device"
-              % (args.reduce, report["cloud_points_before"], report.get("cloud_points_before_filter", report.get("cloud_points_before_outliers", report["cloud_points"])),
+              % (args.reduce, report["cloud_points_before"], report.get("cloud_points_before_filter", report.get("cloud_points_before_outliers", after_outliers)),
                  report["reference_points_before"],
                  report["reference_points"], "/".join("%d" % r for r in report["thin_rounds"]),
                  "/".join("%.2f" % m for m in report["thin_device_ms"])))
     if args.neighbour_radius > 0:
         print("points with fewer than %d others within %g dropped: cloud %d -> %d points, %.2f ms on device"
               % (args.min_neighbours, args.neighbour_radius, report["cloud_points_before_filter"],
-                 report.get("cloud_points_before_outliers", report["cloud_points"]), report["filter_device_ms"]))
+                 report.get("cloud_points_before_outliers", after_outliers), report["filter_device_ms"]))
     if args.outlier_radius > 0:
         print("points with a mean distance above %g to their %d nearest within %g (%g standard deviations) dropped: cloud %d -> %d "
               "points, %.2f ms on device"
               % (report["outlier_threshold"], args.outlier_k, args.outlier_radius, args.outlier_std,
-                 report["cloud_points_before_outliers"], report["cloud_points"], report["outlier_device_ms"]))
+                 report["cloud_points_before_outliers"], after_outliers, report["outlier_device_ms"]))
+    if args.component_radius > 0:
+        print("%d components of points within %g of each other, those of fewer than %d points dropped: cloud %d -> %d points, "
+              "%.2f ms on device"
+              % (report["components"], args.component_radius, args.min_component, report["cloud_points_before_components"],
+                 report["cloud_points"], report["component_device_ms"]))
     return 0
 
 

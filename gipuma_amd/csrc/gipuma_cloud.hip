@@ -25,17 +25,21 @@
 // cell varies from run to run.  The contract's result does not depend on that order: the search carries (d2, j) compared
 // lexicographically, and a cell's points are all visited or all skipped.
 //
-// The same grid has three more clients, on the cloud's own box: thinning it to a minimum point spacing (namespace thin,
+// The same grid has four more clients, on the cloud's own box: thinning it to a minimum point spacing (namespace thin,
 // DESIGN.md 15, gipuma_hip_cloud_thin), counting each point's neighbours within a radius (namespace support, DESIGN.md
-// 16, gipuma_hip_cloud_neighbours) and listing each point's k nearest neighbours with their mean distance (namespace knn,
-// DESIGN.md 17, gipuma_hip_cloud_knn).  What they share is written once in namespace cloud.  Device: d2_of (the contract's
-// d2, the search's too) and Reach (the cells a lane visits and a row's records, with kReach: why no neighbour is skipped).
-// Host: Box, lay_out and sort_by_cell, which the search takes for its targets, and OwnGrid, which runs them for the three.
+// 16, gipuma_hip_cloud_neighbours), listing each point's k nearest neighbours with their mean distance (namespace knn,
+// DESIGN.md 17, gipuma_hip_cloud_knn) and -- the fourth, in a unit of its own, gipuma_components.hip -- labelling the
+// connected components of its radius graph (namespace comp, DESIGN.md 18, gipuma_hip_cloud_components).  What they share is
+// written once in namespace cloud, in pm_cloud.h.  Device: d2_of (the contract's d2, the search's too) and Reach (the cells a
+// lane visits and a row's records, with kReach: why no neighbour is skipped).  Host: Box, Layout, OwnGrid, which runs the
+// set-up for the four, and check_args; lay_out and sort_by_cell, which the search takes for its targets, stay here, as do the
+// set-up kernels and the bodies of the host steps that launch them.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
+#include "pm_cloud.h"
 #include "pm_hash.h"
 #include "pm_host.h"
 
@@ -44,78 +48,8 @@ namespace thin { inline int automatic_grid(float longest, float radius); }  // (
 
 namespace cloud {
 
-constexpr int kBlock = 256;        // points per workgroup: 4 wavefronts
 constexpr int kScan = 1024;        // threads of the scan workgroup
 constexpr int kItems = 16;         // cells per thread and chunk of the scan: a chunk is 16384 cells
-constexpr int kBoxBlocks = 1024;   // workgroups (at most) of the first box stage
-constexpr int kMaxGrid = 256;      // cells along the longest axis: at most 2^24 cells
-enum { kEarly = 0, kSearched = 1, kFound = 2, kTargets = 3, kStats = 4 };  // the device counters
-
-struct Grid {
-    float lo[3], hi[3];  // bounding box of the finite targets
-    float h, inv_h;      // cell edge, 1 / h
-    float r2;            // max_dist^2
-    int g[3];            // cells per axis, 1 .. kMaxGrid
-};
-
-struct __align__(16) Rec {  // a sorted point: its coordinates and its index in the caller's array
-    float x, y, z;
-    int32_t j;
-};
-
-// The cell of coordinate p along an axis with g cells: clamp(floor((p - lo) * inv_h), 0, g - 1).  p - lo, the product
-// with inv_h > 0, floorf, the clamp and the conversion are each non-decreasing in p, so cell_of is MONOTONIC in p; the
-// search relies on nothing else about it.  (Clamped as a float, before the conversion: a query far outside the box may
-// give +-inf here, never NaN -- p and lo are finite, inv_h is finite and > 0.)  The clamp is what places a query outside
-// the box: in the nearest cell of the border, which keeps the monotonicity.
-__device__ __forceinline__ int cell_of(float p, float lo, float inv_h, int g)
-{
-    if (g == 1) return 0;
-    const float t = floorf((p - lo) * inv_h);
-    return (int)fminf(fmaxf(t, 0.f), (float)(g - 1));
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// The contract's d2 of a point a and a sorted point b, the one place it is written for every client's kernel.
-__device__ __forceinline__ float d2_of(const Rec &a, const Rec &b)
-{
-    const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
-// The reach of a lane's cell range.  Lane a visits, per axis k, the cells cell_of(fl(a_k - reach)) .. cell_of(fl(a_k +
-// reach)) with reach = fl(kReach * radius).  No neighbour is skipped: let b be finite with d2(a, b) <= r2.
-//   * d2 is a sum of non-negative floats and rounding is monotonic, so fl(d_k * d_k) <= d2 <= r2 = fl(radius * radius)
-//     <= radius^2 (1 + 2^-24) for d_k = fl(a_k - b_k).  Either d_k * d_k < 2^-126, and then |d_k| < 2^-63 < radius, or
-//     the product is rounded with relative error 2^-24: d_k^2 <= radius^2 (1 + 2^-24) / (1 - 2^-24).  A difference of
-//     floats never underflows, |a_k - b_k| <= |d_k| / (1 - 2^-24).  Together the REAL |a_k - b_k| <= radius (1 + 2^-22).
-//   * reach >= 1.01 (1 - 2^-24)^2 radius > 1.009 radius (kReach is 1.01 rounded to a float; no underflow, the grid is
-//     only used for 2^-40 <= radius <= 2^40), so the real x = a_k - reach < a_k - radius (1 + 2^-22) <= b_k.  b_k is a
-//     float and rounding is monotonic: b_k >= fl(x), the value the lane computes.  An overflow to -inf only lowers it.
-//   * cell_of is monotonic: cell_of(b_k) >= cell_of(fl(a_k - reach)).  The upper end is the mirror image.
-// Nothing here depends on how cell_of rounds, only on its monotonicity; the slack of 0.9 % is spent on a bound that
-// needs 2^-22.  Outside 2^-40 .. 2^40 (radius or cell edge) the host takes G = 1: one cell, every point visited.
-// The statement is about this range and any finite b within the radius, whatever a client (thin, support) then asks of b.
-constexpr float kReach = 1.01f;
-inline bool reach_holds(float radius) { return radius >= 0x1p-40f && radius <= 0x1p40f; }
-
-struct Reach {
-    int x0, x1, y0, y1, z0, z1;
-
-    __device__ __forceinline__ Reach(const Rec &a, float reach, const Grid &g)
-        : x0(cell_of(a.x - reach, g.lo[0], g.inv_h, g.g[0])), x1(cell_of(a.x + reach, g.lo[0], g.inv_h, g.g[0])),
-          y0(cell_of(a.y - reach, g.lo[1], g.inv_h, g.g[1])), y1(cell_of(a.y + reach, g.lo[1], g.inv_h, g.g[1])),
-          z0(cell_of(a.z - reach, g.lo[2], g.inv_h, g.g[2])), z1(cell_of(a.z + reach, g.lo[2], g.inv_h, g.g[2])) {}
-    // Cells are numbered x fastest and ends[] is what scatter_kernel leaves: the cells x0 .. x1 of the row (y, z) hold the
-    // one contiguous range sorted[beg .. end), as a row of a shell's face does in search_kernel.
-    __device__ __forceinline__ void row(const uint32_t *__restrict__ ends, const Grid &g, int y, int z, uint32_t &beg, uint32_t &end) const
-    {
-        const int c0 = (z * g.g[1] + y) * g.g[0] + x0;
-        end = ends[c0 + (x1 - x0)];
-        beg = c0 ? ends[c0 - 1] : 0u;
-    }
-};
 
 // min of lo[3] / max of hi[3] over the workgroup, left in lane 0's m[]
 __device__ __forceinline__ void reduce_box(float (*s)[kBlock], float m[6])
@@ -364,51 +298,20 @@ inline int automatic_grid(int64_t n_targets)
     return g < 1 ? 1 : g > kMaxGrid ? kMaxGrid : g;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// The host steps that build the grid, shared by the search and the thinning.  They enqueue on the caller's stream, record
-// no events and allocate only where the name says so: the callers place their timed windows around them.
-// ---------------------------------------------------------------------------------------------------------------------
-inline dim3 blocks_for(uint32_t n) { return dim3((n + kBlock - 1) / kBlock); }
-
-// The box of a cloud's finite points.  enqueue() and read() are two calls, so that a caller may record an event between
-// the kernels and the host's read.
-struct Box {
-    float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};  // lo[3], hi[3]; this where no point is finite
-    float *partial = nullptr, *dev = nullptr;
-    int nblocks = 0;
-
-    int alloc(pm_host::CallScope &sc, uint32_t n)
-    {
-        nblocks = (int)(blocks_for(n).x < (uint32_t)kBoxBlocks ? blocks_for(n).x : (uint32_t)kBoxBlocks);
-        return sc.alloc(partial, 6 * (size_t)nblocks) || sc.alloc(dev, 6) ? GIPUMA_HIP_ERR_DEVICE : 0;
-    }
-    int enqueue(hipStream_t st, const float *pts, uint32_t n) const
-    {
-        hipLaunchKernelGGL(box_partial_kernel, dim3(nblocks), dim3(kBlock), 0, st, pts, n, partial);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(box_final_kernel, dim3(1), dim3(kBlock), 0, st, partial, nblocks, dev);
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-    int read(hipStream_t st)  // (one host read)
-    {
-        HIP_OK(hipMemcpyAsync(v, dev, sizeof v, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        return 0;
-    }
-    bool any_finite() const { return v[0] <= v[3] && v[1] <= v[4] && v[2] <= v[5]; }
-    float longest_extent() const { return fmaxf(fmaxf(fmaxf(0.f, v[3] - v[0]), v[4] - v[1]), v[5] - v[2]); }
-};
+// The set-up kernels' launches: Box::enqueue here, OwnGrid::lay and OwnGrid::sort below (pm_cloud.h declares them).
+int Box::enqueue(hipStream_t st, const float *pts, uint32_t n) const
+{
+    hipLaunchKernelGGL(box_partial_kernel, dim3(nblocks), dim3(kBlock), 0, st, pts, n, partial);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(box_final_kernel, dim3(1), dim3(kBlock), 0, st, partial, nblocks, dev);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
 
 // The grid over a box: one cell edge h for all axes, G cells along the longest one; an axis of zero extent gets one cell.
 // One cell (G = 1: every point visited, the brute force) where a client's shortcut is not proven: h outside 2^-40 .. 2^40
 // (squares would underflow or overflow; an infinite extent ends up here), or the client says that its own derivation does
 // not hold (`shortcut_holds`: the search's kShellSlack wants a finite r2, the thinning's kReach a radius in that range).
-struct Layout {
-    Grid g;
-    uint32_t ncells;
-    int64_t report[4];  // G and the cells along x, y, z, as last_stats[0 .. 3] and the thinning's info[4 .. 7] report them
-};
 inline Layout lay_out(const Box &box, int G, float r2, bool shortcut_holds)
 {
     Layout l;
@@ -450,42 +353,41 @@ int sort_by_cell(hipStream_t st, const float *pts, uint32_t n, const Layout &l, 
     return 0;
 }
 
-// A cloud sorted on a grid over its OWN box: the host set-up of the thinning, the neighbour count and the k-NN lists.  The steps are calls of
-// their own, as Box's are, so that a caller's event and its own memsets keep their places on the stream.
-struct OwnGrid {
-    Box box;        // (the caller allocates it, before its first event)
-    Layout l = {};  // (the report stays 0 where no point is finite)
-    bool any = false;
-    Rec *sorted = nullptr;
-    uint32_t *cells = nullptr, *counters = nullptr;
-    int32_t *cellid = nullptr;
+// OwnGrid's two steps that launch (pm_cloud.h): the box kernels and the host's read, then the layout, the buffers and the
+// memsets; the counting sort.
+int OwnGrid::lay(pm_host::CallScope &sc, const float *pts, uint32_t n, float radius, int grid, int n_counters)
+{
+    if (const int rc = box.enqueue(sc.st, pts, n)) return rc;
+    if (const int rc = box.read(sc.st)) return rc;
+    if (!(any = box.any_finite())) return 0;
+    l = lay_out(box, grid ? grid : thin::automatic_grid(box.longest_extent(), radius), radius * radius, reach_holds(radius));
+    if (sc.alloc(cells, l.ncells) || sc.alloc(counters, n_counters) || sc.alloc(cellid, n) || sc.alloc(sorted, n))
+        return GIPUMA_HIP_ERR_DEVICE;
+    HIP_OK(hipMemsetAsync(cells, 0, sizeof(uint32_t) * l.ncells, sc.st));
+    HIP_OK(hipMemsetAsync(counters, 0, sizeof(uint32_t) * n_counters, sc.st));
+    return 0;
+}
 
-    // the box kernels and the host's read; where a point is finite (`any`) the layout (thin's automatic G for grid 0, one
-    // cell unless reach_holds), the buffers and the memsets of the cells and of the caller's n_counters counters
-    int lay(pm_host::CallScope &sc, const float *pts, uint32_t n, float radius, int grid, int n_counters)
-    {
-        if (const int rc = box.enqueue(sc.st, pts, n)) return rc;
-        if (const int rc = box.read(sc.st)) return rc;
-        if (!(any = box.any_finite())) return 0;
-        l = lay_out(box, grid ? grid : thin::automatic_grid(box.longest_extent(), radius), radius * radius, reach_holds(radius));
-        if (sc.alloc(cells, l.ncells) || sc.alloc(counters, n_counters) || sc.alloc(cellid, n) || sc.alloc(sorted, n))
-            return GIPUMA_HIP_ERR_DEVICE;
-        HIP_OK(hipMemsetAsync(cells, 0, sizeof(uint32_t) * l.ncells, sc.st));
-        HIP_OK(hipMemsetAsync(counters, 0, sizeof(uint32_t) * n_counters, sc.st));
-        return 0;
-    }
-    // the counting sort: cells[] goes out as the cells' ends, counters[kTargets] as the number of finite points
-    int sort(hipStream_t st, const float *pts, uint32_t n) const
-    {
-        return sort_by_cell<false>(st, pts, n, l, cellid, cells, sorted, nullptr, nullptr, counters, nullptr);
-    }
-    // info[8] of the three calls: kept (knn: complete), dropped (knn: short), not finite, the caller's fourth figure, G, cells x, y, z
-    void report(int64_t info[8], uint32_t n, uint32_t finite, uint32_t kept, uint32_t fourth) const
-    {
-        const int64_t figures[4] = {kept, (int64_t)finite - kept, (int64_t)n - finite, fourth};
-        if (info) memcpy(info, figures, sizeof figures), memcpy(info + 4, l.report, sizeof l.report);
-    }
-};
+int OwnGrid::sort(hipStream_t st, const float *pts, uint32_t n) const
+{
+    return sort_by_cell<false>(st, pts, n, l, cellid, cells, sorted, nullptr, nullptr, counters, nullptr);
+}
+
+// The checks the entry points share (pm_cloud.h), in their order, `what` before every text.  null_pointer: the entry point's own
+// rule; own: the text of the first of its own checks that fails (null: none), reported in its place with own_rc.  The device
+// comes last.
+int check_args(const char *what, int abi_version, int64_t n0, int64_t n1, bool null_pointer, const char *dist_name, float dist,
+               const char *own, int grid, int device_id, int own_rc)
+{
+    if (abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "%s: abi_version mismatch", what);
+    if (n0 < 0 || n1 < 0) return fail(GIPUMA_HIP_ERR_ARG, "%s: negative point count", what);
+    if ((n0 | n1) >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "%s: a cloud may hold at most 2^31 - 1 points", what);
+    if (null_pointer) return fail(GIPUMA_HIP_ERR_ARG, "%s: null pointer with a non-zero point count", what);
+    if (!(dist > 0.f) || !std::isfinite(dist)) return fail(GIPUMA_HIP_ERR_ARG, "%s: %s must be > 0 and finite", what, dist_name);
+    if (own) return fail(own_rc, "%s: %s", what, own);
+    if (grid < 0 || grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "%s: grid must be 0 (automatic) or 1..256", what);
+    return pm_host::check_device(device_id);
+}
 
 }  // namespace cloud
 
@@ -1001,22 +903,6 @@ int run_knn(const gipuma_hip_knn_desc *d, float *d2_dev, int32_t *idx_dev, uint3
     return 0;
 }
 
-// The checks the four entry points share, in their order, `what` before every text.  null_pointer: the entry point's own
-// rule; own: the text of the first of its own checks that fails (null: none), reported in its place with own_rc.  The device
-// comes last.
-int check_args(const char *what, int abi_version, int64_t n0, int64_t n1, bool null_pointer, const char *dist_name, float dist,
-               const char *own, int grid, int device_id, int own_rc = GIPUMA_HIP_ERR_ARG)
-{
-    if (abi_version != GIPUMA_HIP_ABI_VERSION) return fail(GIPUMA_HIP_ERR_ARG, "%s: abi_version mismatch", what);
-    if (n0 < 0 || n1 < 0) return fail(GIPUMA_HIP_ERR_ARG, "%s: negative point count", what);
-    if ((n0 | n1) >= (1ll << 31)) return fail(GIPUMA_HIP_ERR_UNSUPPORTED, "%s: a cloud may hold at most 2^31 - 1 points", what);
-    if (null_pointer) return fail(GIPUMA_HIP_ERR_ARG, "%s: null pointer with a non-zero point count", what);
-    if (!(dist > 0.f) || !std::isfinite(dist)) return fail(GIPUMA_HIP_ERR_ARG, "%s: %s must be > 0 and finite", what, dist_name);
-    if (own) return fail(own_rc, "%s: %s", what, own);
-    if (grid < 0 || grid > cloud::kMaxGrid) return fail(GIPUMA_HIP_ERR_ARG, "%s: grid must be 0 (automatic) or 1..256", what);
-    return pm_host::check_device(device_id);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1024,7 +910,7 @@ extern "C" {
 int gipuma_hip_cloud_nearest(const gipuma_hip_cloud_desc *d, float *d2_dev, int32_t *idx_dev, int64_t counts[2], float *device_ms)
 {
     if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
-    if (const int rc = check_args("cloud", d->abi_version, d->n_queries, d->n_targets,
+    if (const int rc = cloud::check_args("cloud", d->abi_version, d->n_queries, d->n_targets,
                                   (d->n_queries && (!d->queries || !d2_dev || !idx_dev)) || (d->n_targets && !d->targets), "max_dist",
                                   d->max_dist, nullptr, d->grid, d->device_id))
         return rc;
@@ -1043,7 +929,7 @@ int gipuma_hip_cloud_thin(const gipuma_hip_thin_desc *d, uint8_t *keep_dev, int6
 {
     if (!d) return fail(GIPUMA_HIP_ERR_ARG, "null descriptor");
     const char *own = d->order != 0 && d->order != 1 ? "order must be 0 (hashed) or 1 (index)" : nullptr;
-    if (const int rc = check_args("thin", d->abi_version, d->n_points, 0, d->n_points && (!d->points || !keep_dev), "radius", d->radius,
+    if (const int rc = cloud::check_args("thin", d->abi_version, d->n_points, 0, d->n_points && (!d->points || !keep_dev), "radius", d->radius,
                                   own, d->grid, d->device_id))
         return rc;
     return run_thin(d, keep_dev, info, device_ms);
@@ -1056,7 +942,7 @@ int gipuma_hip_cloud_neighbours(const gipuma_hip_neighbours_desc *d, uint32_t *c
     const char *own = d->min_neighbours < 0 ? "min_neighbours must be >= 0"
                       : d->max_count < 0    ? "max_count must be >= 0 (0: exact counts)"
                       : d->max_count > 0 && d->min_neighbours > d->max_count ? "min_neighbours must not exceed a max_count > 0" : nullptr;
-    if (const int rc = check_args("neighbours", d->abi_version, d->n_points, 0, d->n_points && (!d->points || (!count_dev && !keep_dev)),
+    if (const int rc = cloud::check_args("neighbours", d->abi_version, d->n_points, 0, d->n_points && (!d->points || (!count_dev && !keep_dev)),
                                   "radius", d->radius, own, d->grid, d->device_id))
         return rc;
     return run_neighbours(d, count_dev, keep_dev, info, device_ms);
@@ -1069,7 +955,7 @@ int gipuma_hip_cloud_knn(const gipuma_hip_knn_desc *d, float *d2_dev, int32_t *i
     const bool bad_k = d->k < 1 || d->k > knn::kMaxK;
     const bool too_many = !bad_k && (d2_dev || idx_dev) && d->n_points >= ((1ll << 31) + d->k - 1) / d->k;  // n * k >= 2^31
     const char *own = bad_k ? "k must be 1..32" : too_many ? "the lists may hold at most 2^31 - 1 slots (n_points * k)" : nullptr;
-    if (const int rc = check_args("knn", d->abi_version, d->n_points, 0,
+    if (const int rc = cloud::check_args("knn", d->abi_version, d->n_points, 0,
                                   d->n_points && (!d->points || (!d2_dev && !idx_dev && !count_dev && !mean_dev)), "radius", d->radius,
                                   own, d->grid, d->device_id, bad_k ? GIPUMA_HIP_ERR_ARG : GIPUMA_HIP_ERR_UNSUPPORTED))
         return rc;

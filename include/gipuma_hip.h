@@ -514,6 +514,39 @@ typedef struct gipuma_hip_knn_desc {
 int gipuma_hip_cloud_knn(const gipuma_hip_knn_desc *desc, float *d2_dev, int32_t *idx_dev, uint32_t *count_dev,
                          float *mean_dev, int64_t info[8], float *device_ms);
 
+/* ---- the connected components of a cloud's radius graph: dropping its small clumps ----
+ * P: n_points packed float32 xyz.  d2(i, j) and r2 = radius * radius are the thinning's, float32 without contraction; the
+ * edge relation is the neighbour count's radius graph: i ~ j iff i != j by index, both points are finite and d2(i, j) <= r2
+ * (inclusive; inf <= inf holds where r2 = +inf; an exact copy is a neighbour).  d2 is bitwise symmetric, so is the relation.
+ *     P_i not finite in all three coordinates:  label(i) = -1, size(i) = 0, keep(i) = 0 -- and no component contains i
+ *     otherwise:  C(i)     = the connected component of i in the radius graph over the finite points
+ *                 label(i) = min { j : j in C(i) }     (the caller's index)
+ *                 size(i)  = |C(i)|
+ *                 keep(i)  = size(i) >= min_size
+ * A component's smallest index and its cardinality are defined without reference to the grid, to the order the kernels
+ * visit the points in or to how their concurrent unions interleave: all three outputs equal a sequential union-find over
+ * a brute-force edge list in every byte, run after run (tests/components_ref.py).  `grid` is the thinning's and changes the
+ * time only.  n_points = 0 writes nothing.  Blocks until the outputs are complete; the cloud must be complete on
+ * desc->stream's terms when the call is made.  Scratch (about 36 bytes per point and 4 per cell, 16 of them on top of the
+ * neighbour count's) is allocated for the call and freed before it returns, on every error path too. */
+typedef struct gipuma_hip_components_desc {
+    uint32_t abi_version; /* GIPUMA_HIP_ABI_VERSION */
+    int64_t n_points;     /* < 2^31; more: GIPUMA_HIP_ERR_UNSUPPORTED */
+    const float *points;  /* device pointer, packed xyz float32 */
+    float radius;         /* > 0 and finite, else GIPUMA_HIP_ERR_ARG */
+    int32_t min_size;     /* >= 0, else GIPUMA_HIP_ERR_ARG */
+    int32_t grid;         /* 0: automatic; 1..256: cells along the longest axis */
+    int32_t device_id;    /* HIP device ordinal */
+    void *stream;         /* hipStream_t to launch on, NULL = one the library creates for the call */
+} gipuma_hip_components_desc;
+
+/* label_dev: n_points int32, device; size_dev: n_points uint32, device; keep_dev: n_points bytes, device.  Each may be NULL,
+ * not all three where n_points > 0 (GIPUMA_HIP_ERR_ARG).  info (points kept, finite points dropped -- in a component below
+ * min_size --, points not finite, components, cells along the longest axis, cells along x, y and z) and device_ms (HIP
+ * events around everything the call enqueues) may be NULL. */
+int gipuma_hip_cloud_components(const gipuma_hip_components_desc *desc, int32_t *label_dev, uint32_t *size_dev,
+                                uint8_t *keep_dev, int64_t info[8], float *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
