@@ -168,6 +168,16 @@ class KnnDesc(C.Structure):
     ]
 
 
+class NormalsDesc(C.Structure):
+    """gipuma_hip_normals_desc: one device cloud of packed float32 xyz, the radius, the list length k (3..32), the grid (0:
+    automatic), the sign rule (0 largest component, 1 viewpoint, 2 guide) with its viewpoint and guide normals"""
+    _fields_ = [
+        ("abi_version", C.c_uint32), ("n_points", C.c_int64), ("points", C.c_void_p), ("radius", C.c_float),
+        ("k", C.c_int32), ("grid", C.c_int32), ("orient", C.c_int32), ("viewpoint", C.c_float * 3), ("guide", C.c_void_p),
+        ("device_id", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
 # every symbol include/gipuma_hip.h declares: (name, restype, argtypes)
 _FP = C.POINTER(C.c_float)
 SYMBOLS = [
@@ -209,6 +219,8 @@ SYMBOLS = [
                                        _FP]),
     ("gipuma_hip_cloud_components", C.c_int, [C.POINTER(ComponentsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
                                               _FP]),
+    ("gipuma_hip_cloud_normals", C.c_int, [C.POINTER(NormalsDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_int64), _FP]),
 ]
 
 _lib = None

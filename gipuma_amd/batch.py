@@ -45,7 +45,11 @@ MI355X-first differences from the shell loop:
   * --fuse_component_radius r --fuse_min_component N (with --fuse): the fused cloud then loses its small clumps -- every
     connected component of its radius graph (points joined where they lie within r of each other) with fewer than N
     points (gipuma_amd.cloud_eval.drop_small_components) -- after --fuse_outlier_radius, before fused.ply
-    is written and scored.
+    is written and scored;
+  * --fuse_normal_radius r --fuse_normal_k K --fuse_max_normal_angle a (with --fuse): the fused cloud then loses the
+    points whose fused normal is more than a degrees off the normal estimated from their K nearest neighbours within r,
+    and those with fewer than three neighbours there (gipuma_amd.cloud_eval.drop_disagreeing_normals) --
+    after --fuse_component_radius, before fused.ply is written and scored.
 
 Images: what the reference's scripts hand to imread (main.cpp:739-751) -- PNG, JPG (through PIL), binary PGM / PPM.
 Calibration: <p-folder>/<image name>.P (fileIoUtils.h:83-110).
@@ -353,6 +357,14 @@ def parse_args(argv):
                          "than that many points (0: off; DESIGN.md 18)")
     pa.add_argument("--fuse_min_component", type=int, default=None,
                     help="with --fuse_component_radius: the points a component needs for them to stay")
+    pa.add_argument("--fuse_normal_radius", type=float, default=0.0,
+                    help="with --fuse, --fuse_normal_k and --fuse_max_normal_angle: after --fuse_component_radius, drop the "
+                         "fused points whose fused normal is more than that angle off the normal estimated from their k "
+                         "nearest neighbours within this radius, and those with fewer than three neighbours there (0: off; "
+                         "DESIGN.md 19)")
+    pa.add_argument("--fuse_normal_k", type=int, default=None, help="with --fuse_normal_radius: the number of nearest neighbours, 3..32")
+    pa.add_argument("--fuse_max_normal_angle", type=float, default=None,
+                    help="with --fuse_normal_radius: the angle allowed between the fused normal and the estimate, 0..90 degrees")
     args = pa.parse_args(argv)
     # the reference parses these with sscanf("%f") into float fields (main.cpp:300-360)
     for k in ("cost_gamma", "depth_min", "depth_max", "min_angle", "max_angle", "cam_scale", "disp_thresh",
@@ -383,6 +395,11 @@ def parse_args(argv):
     check_component_args(pa, args, "fuse_component_radius", "fuse_min_component")
     if args.fuse_component_radius > 0 and not args.fuse:
         pa.error("--fuse_component_radius filters the fused cloud: it needs --fuse")
+    from .cloud_eval import check_normal_args
+    check_normal_args(pa, args, "fuse_normal_radius", "fuse_normal_k", "fuse_max_normal_angle")
+    args.fuse_max_normal_angle = args.fuse_max_normal_angle or 0.0
+    if args.fuse_normal_radius > 0 and not args.fuse:
+        pa.error("--fuse_normal_radius filters the fused cloud: it needs --fuse")
     if args.levels < 1:
         raise SystemExit("--levels must be >= 1")
     args.level_iterations = [int(v) for v in args.level_iterations.split(",") if v] or \
@@ -437,6 +454,14 @@ def fuse_solved(scan):
                                                        args.fuse_component_radius, args.fuse_min_component,
                                                        device_id=scan.dev[0].device.index, return_info=True)
         filtered.update({"points_before_components": int(len(points)), "components": c["components"], "component_device_ms": ms})
+        points = points[kept]
+    if args.fuse_normal_radius > 0:  # (then the points fused at a wrong plane among good neighbours: the first stage that reads the normals)
+        from . import cloud_eval
+        kept, ms, _ = cloud_eval.drop_disagreeing_normals(np.stack([points["x"], points["y"], points["z"]], axis=-1),
+                                                          np.stack([points["nx"], points["ny"], points["nz"]], axis=-1),
+                                                          args.fuse_normal_radius, args.fuse_normal_k, args.fuse_max_normal_angle,
+                                                          device_id=scan.dev[0].device.index, return_info=True)
+        filtered.update({"points_before_normals": int(len(points)), "normal_device_ms": ms})
         points = points[kept]
     dmb.write_points_ply(os.path.join(args.output_folder, "fused.ply"), points)
     scan.fused_xyz = np.stack([points["x"], points["y"], points["z"]], axis=-1)  # (for --eval_cloud)

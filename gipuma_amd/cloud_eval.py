@@ -1,11 +1,13 @@
 """Score a point cloud against a reference cloud on the GPU: accuracy and completeness, after thinning
 the cloud to a minimum point spacing, dropping its isolated points, dropping its
-statistical outliers and dropping its small clumps when asked to.
+statistical outliers, dropping its small clumps and dropping the points whose normal
+disagrees with the surface around them when asked to.
 
     python -m gipuma_amd.cloud_eval --cloud fused.ply --reference gt.ply --max_dist 20 --thresholds 0.5,1,2 \\
         [--reduce 0.2 [--reduce_reference] [--seed N]] [--neighbour_radius 1 --min_neighbours 8] \\
         [--outlier_radius 1 --outlier_k 16 --outlier_std 2] [--component_radius 1 --min_component 100] \\
-        [--write_cloud scored.ply] [--output report.json]
+        [--normal_radius 1 --normal_k 16 --max_normal_angle 30] [--write_cloud scored.ply [--estimated_normals]] \\
+        [--output report.json]
 
 DTU -- the data set this project is calibrated on -- scores a reconstruction cloud against cloud: accuracy is the distance
 from each reconstructed point to the nearest reference point, completeness the same the other way round, distances beyond
@@ -26,7 +28,13 @@ filter sees a CLUMP: forty points fused at a wrong depth have thirty-nine neighb
 --component_radius / --min_component drop every connected component of the radius graph -- points joined where they lie
 within the radius of each other -- that has fewer than min_component points (gipuma_hip_cloud_components,
 gipuma_amd/csrc/gipuma_components.hip; `components`, `component_labels`, `drop_small_components`), after the three;
-`component_labels` also segments a cloud into its objects.  --write_cloud writes the cloud as it is scored.  Not part of the score here: DTU's observability masks and ground-plane removal.
+`component_labels` also segments a cloud into its objects.  None of the four reads the normals a fused cloud carries, which
+are averaged plane hypotheses, not the normals of the surface the points form.  `normals` / `estimate_normals`
+(gipuma_hip_cloud_normals, gipuma_amd/csrc/gipuma_normals.hip) estimate the geometric normal and the surface variation of
+every point from its k nearest neighbours within a radius; --normal_radius / --normal_k / --max_normal_angle drop every
+point of the cloud whose own normal (the PLY's nx, ny, nz) is more than that angle off the estimate, and every point with
+fewer than three neighbours there (`normal_agreement`, `drop_disagreeing_normals`), after the four; --estimated_normals
+writes the estimates in place of the file's normals.  --write_cloud writes the cloud as it is scored.  Not part of the score here: DTU's observability masks and ground-plane removal.
 """
 import argparse
 import ctypes as C
@@ -36,6 +44,7 @@ import sys
 import numpy as np
 
 from . import abi, dmb
+from .cameras import cos_f32
 
 THRESHOLDS = (0.5, 1.0, 2.0)
 _STATS = ("grid", "cells_x", "cells_y", "cells_z", "early_out", "searched")
@@ -43,6 +52,7 @@ ORDERS = {"hashed": 0, "index": 1}
 _THIN_INFO = ("kept", "dropped", "not_finite", "rounds", "grid", "cells_x", "cells_y", "cells_z")
 _KNN_INFO = ("complete", "short", "not_finite", "unused", "grid", "cells_x", "cells_y", "cells_z")
 _COMPONENT_INFO = ("kept", "dropped", "not_finite", "components", "grid", "cells_x", "cells_y", "cells_z")
+_NORMAL_INFO = ("estimated", "short", "not_finite", "flipped", "grid", "cells_x", "cells_y", "cells_z")
 _NEIGHBOUR_INFO = ("kept", "dropped", "not_finite", "saturated", "grid", "cells_x", "cells_y", "cells_z")
 
 
@@ -261,6 +271,79 @@ def drop_small_components(points, radius, min_size, grid=0, device_id=0, return_
     return (_indices(keep), ms, info) if return_info else _indices(keep)
 
 
+def normals(points, radius, k, orient=0, viewpoint=None, guide=None, grid=0, device_id=0, normal=True, variation=True, count=True,
+            scatter=False):
+    """The contract of gipuma_hip_cloud_normals on the (n, 3) cloud `points` (a numpy array or a torch tensor; a device
+    tensor is passed by pointer): (normal, variation, count, scatter, device_ms, info) -- torch tensors on the device, normal
+    float32 (n, 3), variation float32 (n,), count int32 (n,) holding the uint32 m's bits, scatter float64 (n, 6), the upper
+    triangle of C, each None where its switch is False; info dict(estimated, short, not_finite, flipped, grid, cells_x,
+    cells_y, cells_z).  orient 0: the component of largest magnitude positive; 1: towards `viewpoint` (3 numbers); 2: along
+    the (n, 3) normals `guide`."""
+    if int(orient) == 1 and viewpoint is None:
+        raise ValueError("orient 1 needs a viewpoint")
+    torch, lib, d, dev, held = _open("a cloud's normals", abi.NormalsDesc, device_id)
+    d.points, d.n_points = _device_cloud(points, dev, held)
+    d.radius, d.k, d.grid, d.orient = float(radius), int(k), int(grid), int(orient)
+    if viewpoint is not None:
+        d.viewpoint = (C.c_float * 3)(*[float(v) for v in viewpoint])
+    if guide is not None:
+        d.guide, n_guide = _device_cloud(guide, dev, held)
+        if n_guide != d.n_points:
+            raise ValueError("the guide holds %d normals for %d points" % (n_guide, d.n_points))
+    outs = (torch.empty((d.n_points, 3), dtype=torch.float32, device=dev) if normal else None,
+            torch.empty(d.n_points, dtype=torch.float32, device=dev) if variation else None,
+            torch.empty(d.n_points, dtype=torch.int32, device=dev) if count else None,
+            torch.empty((d.n_points, 6), dtype=torch.float64, device=dev) if scatter else None)
+    info, ms = _call(torch, lib, "gipuma_hip_cloud_normals", d, dev, outs, _NORMAL_INFO)
+    return outs + (ms, info)
+
+
+def estimate_normals(points, radius, k, orient=0, viewpoint=None, guide=None, grid=0, device_id=0, return_info=False):
+    """The geometric normal and the surface variation of every point of the cloud from its (at most) k nearest other finite
+    points within `radius`: the eigenvector of the smallest eigenvalue of their covariance, the point
+    included, and that eigenvalue's share of the three.  Returns (normal (n, 3) float32, variation (n,) float32), numpy;
+    ((0, 0, 0), +inf) for a point that is not finite, has fewer than three neighbours there or whose neighbourhood is a single
+    place; with return_info also device_ms and dict(estimated, short, not_finite, flipped, grid, cells_x, cells_y, cells_z)."""
+    nrm, var, _, _, ms, info = normals(points, radius, k, orient, viewpoint, guide, grid, device_id, count=False)
+    out = nrm.cpu().numpy(), var.cpu().numpy()
+    return out + (ms, info) if return_info else out
+
+
+def normal_agreement(estimated, given):
+    """|n . g| / |g| per point in float64 (host side): how well the normals `given` agree with the `estimated` ones, 1 for
+    parallel or anti-parallel, 0 for perpendicular -- and 0 where the estimate is the zero vector (no estimate) or g is zero
+    or not finite."""
+    e = np.ascontiguousarray(estimated, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    g = np.ascontiguousarray(given, dtype=np.float32).reshape(-1, 3).astype(np.float64)
+    if len(e) != len(g):
+        raise ValueError("%d estimates for %d given normals" % (len(e), len(g)))
+    with np.errstate(all="ignore"):
+        norm = np.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
+        a = np.abs((e[:, 0] * g[:, 0] + e[:, 1] * g[:, 1]) + e[:, 2] * g[:, 2]) / norm
+    bad = ~np.isfinite(g).all(axis=1) | ~(norm > 0) | ~np.isfinite(norm) | ~e.any(axis=1) | ~np.isfinite(a)
+    return np.where(bad, 0.0, a)
+
+
+def _host_normals(given):
+    import torch
+    return given.detach().cpu().numpy() if isinstance(given, torch.Tensor) else np.asarray(given)
+
+
+def drop_disagreeing_normals(points, given, radius, k, max_angle_deg, grid=0, device_id=0, return_info=False):
+    """Drops the points of a cloud whose own normal disagrees with the surface around them: a point is kept
+    iff it has an estimated normal (estimate_normals: at least three neighbours within `radius`, not all in one place) and
+    normal_agreement(estimate, given) >= float32(cos(max_angle_deg * pi / 180)), the cosine made in double.  `given`: the (n,
+    3) normals the cloud carries.  Returns the ascending int64 indices of the kept points (numpy), like `thin`; with
+    return_info also device_ms and dict(estimated, short, not_finite, flipped, grid, cells_x, cells_y, cells_z)."""
+    if not (0 <= max_angle_deg <= 90):
+        raise ValueError("max_angle_deg must be 0..90, got %r" % (max_angle_deg,))
+    nrm, _, _, _, ms, info = normals(points, radius, k, 0, None, None, grid, device_id, variation=False, count=False)
+    est = nrm.cpu().numpy()
+    keep = est.any(axis=1) & (normal_agreement(est, _host_normals(given)) >= float(cos_f32(max_angle_deg)))
+    kept = np.nonzero(keep)[0].astype(np.int64)
+    return (kept, ms, info) if return_info else kept
+
+
 def direction_score(d2, thresholds):
     """One direction of the score from its squared distances (float32, +inf: none): ({mean, median, found, none} over the
     points that found a neighbour, [share of ALL points with d <= tau for tau in thresholds] -- "none" is a miss)."""
@@ -295,7 +378,7 @@ def _reduced(a, radius, seed, device_id):
 
 def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device_id=0, reduce=0.0, reduce_reference=False,
           seed=0, neighbour_radius=0.0, min_neighbours=0, return_indices=False, outlier_radius=0.0, outlier_k=0, outlier_std=0.0,
-          component_radius=0.0, min_component=0):
+          component_radius=0.0, min_component=0, normal_radius=0.0, normal_k=0, max_normal_angle=0.0, cloud_normals=None):
     """Both directions of the score.  accuracy: {mean, median, found, none} of d = sqrt(d2) (float64, on the host) over
     the cloud's points that found a reference point within max_dist; completeness: the same over the reference's points;
     precision / recall per threshold: the share of ALL cloud / reference points with d <= tau; fscore = 2PR / (P + R), 0
@@ -311,7 +394,10 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
     cloud_points_before_outliers and outlier_device_ms.  component_radius > 0: the cloud -- never the reference -- then
     loses its small clumps (drop_small_components with min_component), after the three, before both searches; the report
     then also carries component_radius, min_component, components, cloud_points_before_components and
-    component_device_ms.  return_indices: (report, the ascending indices into `cloud` of
+    component_device_ms.  normal_radius > 0: the cloud -- never the reference -- then loses the points whose normal in
+    `cloud_normals` (an (n, 3) array, row for row the cloud's) disagrees with the estimate (drop_disagreeing_normals with
+    normal_k and max_normal_angle), after the four, before both searches; the report then also carries normal_radius,
+    normal_k, max_normal_angle, cloud_points_before_normals and normal_device_ms.  return_indices: (report, the ascending indices into `cloud` of
     the points scored, or None where all were)."""
     thresholds = [float(t) for t in thresholds]
     if not (reduce >= 0 and np.isfinite(reduce)):
@@ -330,6 +416,14 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
         raise ValueError("component_radius must be >= 0 and finite, got %r" % (component_radius,))
     if int(min_component) != min_component or not 0 <= min_component < 2 ** 31:
         raise ValueError("min_component must be an integer 0 .. 2^31 - 1, got %r" % (min_component,))
+    if not (normal_radius >= 0 and np.isfinite(normal_radius)):
+        raise ValueError("normal_radius must be >= 0 and finite, got %r" % (normal_radius,))
+    if normal_radius > 0 and (int(normal_k) != normal_k or not 3 <= normal_k <= 32):
+        raise ValueError("normal_k must be an integer 3..32, got %r" % (normal_k,))
+    if normal_radius > 0 and not (0 <= max_normal_angle <= 90):
+        raise ValueError("max_normal_angle must be 0..90 degrees, got %r" % (max_normal_angle,))
+    if normal_radius > 0 and (cloud_normals is None or tuple(cloud_normals.shape) != (int(cloud.shape[0]), 3)):
+        raise ValueError("normal_radius needs cloud_normals, an (n, 3) array of the cloud's own normals")
     before, thinned, indices = (int(cloud.shape[0]), int(reference.shape[0])), [], None
     if reduce > 0:
         cloud, indices, t = _reduced(cloud, reduce, seed, device_id)
@@ -351,6 +445,12 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
         kept, component_ms, comp_info = drop_small_components(cloud, component_radius, int(min_component), device_id=device_id,
                                                            return_info=True)
         cloud, indices = _taken(cloud, kept, device_id), kept if indices is None else indices[kept]
+    if normal_radius > 0:  # (the points fused at a wrong plane among good neighbours: only the normals tell them apart)
+        before_normals = int(cloud.shape[0])
+        given = _host_normals(cloud_normals)
+        kept, normal_ms, _ = drop_disagreeing_normals(cloud, given if indices is None else given[indices], normal_radius, int(normal_k),
+                                                      max_normal_angle, device_id=device_id, return_info=True)
+        cloud, indices = _taken(cloud, kept, device_id), kept if indices is None else indices[kept]
     a_d2, _, a_ms, a_info = nearest(cloud, reference, max_dist, grid, device_id, return_info=True)
     c_d2, _, c_ms, c_info = nearest(reference, cloud, max_dist, grid, device_id, return_info=True)
     out = combine(*direction_score(a_d2, thresholds), *direction_score(c_d2, thresholds), thresholds)
@@ -371,6 +471,9 @@ def score(cloud, reference, max_dist=20.0, thresholds=THRESHOLDS, grid=0, device
         out.update({"component_radius": float(component_radius), "min_component": int(min_component),
                     "components": comp_info["components"], "cloud_points_before_components": before_components,
                     "component_device_ms": component_ms})
+    if normal_radius > 0:
+        out.update({"normal_radius": float(normal_radius), "normal_k": int(normal_k), "max_normal_angle": float(max_normal_angle),
+                    "cloud_points_before_normals": before_normals, "normal_device_ms": normal_ms})
     return (out, indices) if return_indices else out
 
 
@@ -402,6 +505,22 @@ def check_component_args(pa, args, radius, size):
     setattr(args, radius, r), setattr(args, size, n or 0)
 
 
+def check_normal_args(pa, args, radius, k, angle, angle_optional=False):
+    """the three options of the normal filter (this command's and batch's --fuse_* ones): they need each other, the radius
+    goes through float32; off: radius 0.0, k 0, angle None.  angle_optional (--estimated_normals): the radius and k may come
+    without the angle -- the estimate alone, nothing is dropped.  The filter is on iff the angle is given."""
+    r, kk, a = float(np.float32(getattr(args, radius))), getattr(args, k), getattr(args, angle)
+    if not (r >= 0 and np.isfinite(r)):
+        pa.error("--%s must be >= 0 and finite (0: off)" % radius)
+    if (r > 0) != (kk is not None) or (a is not None and not r > 0) or (a is None and r > 0 and not angle_optional):
+        pa.error("--%s, --%s and --%s need each other" % (radius, k, angle))
+    if kk is not None and not 3 <= kk <= 32:
+        pa.error("--%s must be 3..32" % k)
+    if a is not None and not (0 <= a <= 90):
+        pa.error("--%s must be 0..90 degrees" % angle)
+    setattr(args, radius, r), setattr(args, k, kk or 0)
+
+
 def parse_args(argv):
     pa = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     pa.add_argument("--cloud", required=True, help="the reconstruction, a PLY file (ascii or binary_little_endian)")
@@ -430,10 +549,21 @@ def parse_args(argv):
                          "-- has fewer than that many points (0: off)")
     pa.add_argument("--min_component", type=int, default=None,
                     help="with --component_radius: the points a component needs for them to stay")
+    pa.add_argument("--normal_radius", type=float, default=0.0,
+                    help="with --normal_k and --max_normal_angle: after the four other stages, drop the cloud's points whose "
+                         "own normal (nx, ny, nz of --cloud) is more than that angle off the normal estimated from their k "
+                         "nearest neighbours within this radius, and those with fewer than three neighbours there (0: off); "
+                         "with --estimated_normals alone: the radius of the estimate")
+    pa.add_argument("--normal_k", type=int, default=None, help="with --normal_radius: the number of nearest neighbours, 3..32")
+    pa.add_argument("--max_normal_angle", type=float, default=None,
+                    help="with --normal_radius: the angle allowed between a point's normal and the estimate, 0..90 degrees")
     pa.add_argument("--write_cloud", default=None,
-                    help="write the cloud as it is scored, after --reduce, --neighbour_radius, --outlier_radius and / or "
-                         "--component_radius, as a binary PLY with "
+                    help="write the cloud as it is scored, after --reduce, --neighbour_radius, --outlier_radius, "
+                         "--component_radius and / or --normal_radius, as a binary PLY with "
                          "every vertex property of --cloud")
+    pa.add_argument("--estimated_normals", action="store_true",
+                    help="with --write_cloud, --normal_radius and --normal_k: the written nx, ny, nz are the normals estimated "
+                         "on the scored cloud, along the file's own normals where it has them")
     pa.add_argument("--device", type=int, default=0)
     pa.add_argument("--output", default=None, help="write the report (JSON) here")
     args = pa.parse_args(argv)
@@ -465,21 +595,48 @@ def parse_args(argv):
     args.min_neighbours = args.min_neighbours or 0
     check_outlier_args(pa, args, "outlier_radius", "outlier_k", "outlier_std")
     check_component_args(pa, args, "component_radius", "min_component")
+    check_normal_args(pa, args, "normal_radius", "normal_k", "max_normal_angle", angle_optional=args.estimated_normals)
+    if args.estimated_normals and (args.write_cloud is None or not args.normal_radius > 0):
+        pa.error("--estimated_normals needs --write_cloud, --normal_radius and --normal_k")
     return args
+
+
+def _with_estimated_normals(vertices, own, radius, k, device_id):
+    """the vertices with nx, ny, nz (added behind the other properties where the file has none) set to the estimates on these
+    very vertices, along the normals `own` where there are any, else with the largest component positive"""
+    xyz = np.stack([vertices[c].astype(np.float32) for c in ("x", "y", "z")], axis=-1)
+    est, _ = estimate_normals(xyz, radius, k, orient=0 if own is None else 2, guide=own, device_id=device_id)
+    extra = [(c, "<f4") for c in ("nx", "ny", "nz") if c not in vertices.dtype.names]
+    out = np.empty(len(vertices), dtype=np.dtype(vertices.dtype.descr + extra))
+    for name in vertices.dtype.names:
+        out[name] = vertices[name]
+    for a, c in enumerate(("nx", "ny", "nz")):
+        out[c] = est[:, a]
+    return out
 
 
 def main(argv=None):
     args = parse_args(argv)
-    vertices = dmb.read_ply_vertices(args.cloud) if args.write_cloud else None  # (refused before anything is computed)
+    filtering = args.max_normal_angle is not None  # (else --normal_radius and --normal_k serve --estimated_normals alone)
+    vertices = dmb.read_ply_vertices(args.cloud) if args.write_cloud or filtering else None  # (refused before anything is computed)
+    has_normals = vertices is not None and all(c in (vertices.dtype.names or ()) for c in ("nx", "ny", "nz"))
+    if filtering and not has_normals:
+        raise ValueError("%s: --normal_radius compares the cloud's own normals: the file has no nx, ny, nz" % args.cloud)
+    own = np.stack([vertices[c].astype(np.float32) for c in ("nx", "ny", "nz")], axis=-1) if has_normals else None
     report, indices = score(dmb.read_ply_xyz(args.cloud), dmb.read_ply_xyz(args.reference), args.max_dist, args.thresholds,
                             grid=args.grid, device_id=args.device, reduce=args.reduce, reduce_reference=args.reduce_reference,
                             seed=args.seed, neighbour_radius=args.neighbour_radius, min_neighbours=args.min_neighbours,
                             return_indices=True, outlier_radius=args.outlier_radius, outlier_k=args.outlier_k,
                             outlier_std=args.outlier_std, component_radius=args.component_radius,
-                            min_component=args.min_component)
+                            min_component=args.min_component, **(dict(normal_radius=args.normal_radius, normal_k=args.normal_k,
+                            max_normal_angle=args.max_normal_angle, cloud_normals=own) if filtering else {}))
     report.update({"cloud": args.cloud, "reference": args.reference})
     if args.write_cloud:
-        dmb.write_ply_vertices(args.write_cloud, vertices if indices is None else vertices[indices])
+        scored = vertices if indices is None else vertices[indices]
+        if args.estimated_normals:
+            scored = _with_estimated_normals(scored, own if indices is None or own is None else own[indices], args.normal_radius,
+                                             args.normal_k, args.device)
+        dmb.write_ply_vertices(args.write_cloud, scored)
     if args.output:
         with open(args.output, "w") as f:
             json.dump(report, f, indent=1)
@@ -489,7 +646,8 @@ def main(argv=None):
              report["completeness"]["mean"], report["completeness"]["median"], report["completeness"]["found"],
              report["reference_points"], "/".join("%.4f" % f for f in report["fscore"]),
              "/".join("%g" % t for t in args.thresholds), report["accuracy_device_ms"], report["completeness_device_ms"]))
-    after_outliers = report.get("cloud_points_before_components", report["cloud_points"])  # (what the earlier stages left)
+    after_components = report.get("cloud_points_before_normals", report["cloud_points"])
+    after_outliers = report.get("cloud_points_before_components", after_components)  # (what the earlier stages left)
     if args.reduce > 0:
         print("thinned to a spacing of %g first: cloud %d -> %d points, reference %d -> %d, %s rounds, %s ms on device"
               % (args.reduce, report["cloud_points_before"], report.get("cloud_points_before_filter", report.get("cloud_points_before_outliers", after_outliers)),
@@ -509,7 +667,12 @@ def main(argv=None):
         print("%d components of points within %g of each other, those of fewer than %d points dropped: cloud %d -> %d points, "
               "%.2f ms on device"
               % (report["components"], args.component_radius, args.min_component, report["cloud_points_before_components"],
-                 report["cloud_points"], report["component_device_ms"]))
+                 after_components, report["component_device_ms"]))
+    if filtering:
+        print("points whose normal is more than %g degrees off the one estimated from their %d nearest within %g dropped: cloud %d -> "
+              "%d points, %.2f ms on device"
+              % (args.max_normal_angle, args.normal_k, args.normal_radius, report["cloud_points_before_normals"],
+                 report["cloud_points"], report["normal_device_ms"]))
     return 0
 
 

@@ -634,10 +634,7 @@ __global__ __launch_bounds__(kBlock) void clear_kernel(uint32_t n, uint32_t slot
 }
 
 // *n_sorted: the number of sorted (finite) points, as the histogram left it on the device.  The list is ascending in
-// (d2, j); an empty slot is (+inf, -1) and indices compare UNSIGNED, so that -1 loses to every real index: where r2 = +inf
-// a neighbour whose d2 overflowed to +inf (inf <= inf) displaces an empty slot and ties are still decided by the index.
-// A record that passes the gate is below the last slot; it is carried down the list: each slot keeps the smaller of itself
-// and the carry and hands the larger on, and what falls out of slot K - 1 is the old last pair.
+// (d2, j), an empty slot is (+inf, -1): cloud::nearest_lists (pm_cloud.h), the walk and the compare-and-carry insertion.
 template <int K>
 __global__ __launch_bounds__(kBlock) void topk_kernel(const Rec *__restrict__ sorted, const uint32_t *__restrict__ ends,
                                                       const uint32_t *__restrict__ n_sorted, Grid g, float reach, int k, double inv_k,
@@ -649,31 +646,9 @@ __global__ __launch_bounds__(kBlock) void topk_kernel(const Rec *__restrict__ so
     bool complete = false, is_short = false;
     if (pos < *n_sorted) {
         const Rec a = sorted[pos];
-        const Reach r(a, reach, g);
         float d[K];
         uint32_t j[K];
-#pragma unroll
-        for (int s = 0; s < K; ++s) d[s] = INFINITY, j[s] = ~0u;
-        for (int z = r.z0; z <= r.z1; ++z)
-            for (int y = r.y0; y <= r.y1; ++y) {
-                uint32_t p, end;
-                for (r.row(ends, g, y, z, p, end); p < end; ++p) {
-                    const Rec b = sorted[p];
-                    float cd = d2_of(a, b);
-                    uint32_t cj = (uint32_t)b.j;
-                    if (!(cd <= g.r2) || p == pos || !(cd < d[K - 1] || (cd == d[K - 1] && cj < j[K - 1]))) continue;
-#pragma unroll
-                    for (int s = 0; s < K; ++s) {
-                        const bool below = cd < d[s] || (cd == d[s] && cj < j[s]);
-                        const float td = d[s];
-                        const uint32_t tj = j[s];
-                        d[s] = below ? cd : td;
-                        j[s] = below ? cj : tj;
-                        cd = below ? td : cd;
-                        cj = below ? tj : cj;
-                    }
-                }
-            }
+        nearest_lists<K>(sorted, ends, g, reach, a, pos, d, j);
         // the outputs: slots k .. K - 1 are never written out; m counts the filled ones of the first k
         uint32_t m = 0;
         float sum = 0.f;

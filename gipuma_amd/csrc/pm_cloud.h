@@ -1,6 +1,7 @@
 // pm_cloud.h -- what the cloud units share (gipuma_cloud.hip: search, thinning, neighbour count, k-NN lists; gipuma_components.hip:
-// connected components).  Device: the sorted record, the grid, cell_of, d2_of (the contract's d2) and Reach (the cells a
-// lane visits, with kReach: why no neighbour is skipped).  Host: Box, Layout and OwnGrid, a cloud sorted on a grid over its
+// connected components; gipuma_normals.hip: normals from the k-NN lists).  Device: the sorted record, the grid, cell_of, d2_of
+// (the contract's d2), Reach (the cells a lane visits, with kReach: why no neighbour is skipped) and nearest_lists (a lane's k-NN
+// list).  Host: Box, Layout and OwnGrid, a cloud sorted on a grid over its
 // own box, and check_args, the entry points' common checks.  The set-up KERNELS (box, histogram, scan, scatter) are defined
 // once, in gipuma_cloud.hip; the host steps that launch them are out-of-line functions of that unit, declared here.
 #pragma once
@@ -84,6 +85,42 @@ struct Reach {
     }
 };
 
+// A lane's k-NN list, written once for knn::topk_kernel and nrm::estimate_kernel: the K smallest pairs (d2, j) of
+// the finite points other than sorted[pos] within the radius of a = sorted[pos], ascending.  The lane walks the cells of its Reach
+// row by row.  An empty slot is (+inf, -1) and indices compare UNSIGNED, so that -1 loses to every real index: where r2 = +inf
+// a neighbour whose d2 overflowed to +inf (inf <= inf) displaces an empty slot and ties are still decided by the index.
+// A record that passes the gate is below the last slot; it is carried down the list: each slot keeps the smaller of itself
+// and the carry and hands the larger on, and what falls out of slot K - 1 is the old last pair.  Every loop over the slots is
+// fully unrolled: d[] and j[] are 2K named registers, never indexed at run time.
+template <int K>
+__device__ __forceinline__ void nearest_lists(const Rec *__restrict__ sorted, const uint32_t *__restrict__ ends, const Grid &g, float reach,
+                                              const Rec &a, uint32_t pos, float (&d)[K], uint32_t (&j)[K])
+{
+    const Reach r(a, reach, g);
+#pragma unroll
+    for (int s = 0; s < K; ++s) d[s] = INFINITY, j[s] = ~0u;
+    for (int z = r.z0; z <= r.z1; ++z)
+        for (int y = r.y0; y <= r.y1; ++y) {
+            uint32_t p, end;
+            for (r.row(ends, g, y, z, p, end); p < end; ++p) {
+                const Rec b = sorted[p];
+                float cd = d2_of(a, b);
+                uint32_t cj = (uint32_t)b.j;
+                if (!(cd <= g.r2) || p == pos || !(cd < d[K - 1] || (cd == d[K - 1] && cj < j[K - 1]))) continue;
+#pragma unroll
+                for (int s = 0; s < K; ++s) {
+                    const bool below = cd < d[s] || (cd == d[s] && cj < j[s]);
+                    const float td = d[s];
+                    const uint32_t tj = j[s];
+                    d[s] = below ? cd : td;
+                    j[s] = below ? cj : tj;
+                    cd = below ? td : cd;
+                    cj = below ? tj : cj;
+                }
+            }
+        }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The host steps that build the grid.  They enqueue on the caller's stream, record no events and allocate only where the
 // name says so: the callers place their timed windows around them.  The steps that launch a set-up kernel are defined in
@@ -123,8 +160,8 @@ struct Layout {
     int64_t report[4];  // G and the cells along x, y, z, as last_stats[0 .. 3] and the thinning's info[4 .. 7] report them
 };
 
-// A cloud sorted on a grid over its OWN box: the host set-up of the thinning, the neighbour count, the k-NN lists and the
-// connected components.  The steps are calls of their own, as Box's are, so that a caller's event and its own memsets keep
+// A cloud sorted on a grid over its OWN box: the host set-up of the thinning, the neighbour count, the k-NN lists, the
+// connected components and the normals.  The steps are calls of their own, as Box's are, so that a caller's event and its own memsets keep
 // their places on the stream.
 struct OwnGrid {
     Box box;        // (the caller allocates it, before its first event)

@@ -547,6 +547,52 @@ typedef struct gipuma_hip_components_desc {
 int gipuma_hip_cloud_components(const gipuma_hip_components_desc *desc, int32_t *label_dev, uint32_t *size_dev,
                                 uint8_t *keep_dev, int64_t info[8], float *device_ms);
 
+/* ---- a cloud's normals and surface variation from its k nearest neighbours ----
+ * P: n_points packed float32 xyz.  list(i) and m(i) are gipuma_hip_cloud_knn's: the min(k, |N(i)|) nearest other finite points of
+ * i within the radius, ascending in (d2, j), the same relation, ordering and treatment of copies.
+ *     P_i not finite, or m(i) < 3 ("short"):  normal(i) = (0, 0, 0), variation(i) = +inf, the six entries of C are 0
+ *     otherwise, M = m(i) + 1 (the point itself counts, at d = 0):
+ *         d_s = P_list(i)[s] - P_i per coordinate in float32, then widened to float64               (s ascending)
+ *         S1 = sum_s d_s,  S2 = sum_s d_s d_s^T       (float64, in slot order, from 0; each product is exact in a double)
+ *         C  = M * S2 - S1 S1^T                       (float64, M^2 times the covariance; upper triangle C00 C01 C02 C11 C12 C22)
+ *         trace = (C00 + C11) + C22 <= 0 or not finite ("degenerate": all copies, or overflow): the short values; C is written
+ *         (w, V) = cyclic Jacobi on C in float64, V from the identity: SIX sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r
+ *             the third index; a pair whose a_pq is exactly 0 is skipped; else theta = (a_qq - a_pp) / (2 a_pq),
+ *             t = sgn(theta) / (|theta| + sqrt(theta theta + 1)) with sgn(0) = +1, c = 1 / sqrt(t t + 1), s = t c, h = t a_pq, then
+ *             a_pp -= h; a_qq += h; a_pq = 0; (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq); and for the rows i = 0, 1, 2 of V
+ *             (v_ip, v_iq) = (c v_ip - s v_iq, s v_ip + c v_iq) -- every right-hand side from the values before the rotation
+ *         e = the index of the smallest w = (a_00, a_11, a_22), the lowest index on a tie
+ *         normal(i)    = float32 of column e of V, negated where the sign rule says so
+ *         variation(i) = float32((w_e > 0 ? w_e : 0) / ((w_0 + w_1) + w_2))
+ * The sign rule, on the float32 normal n widened to float64: orient 1: dot = (n_0 (v_0 - p_0) + n_1 (v_1 - p_1)) + n_2 (v_2 - p_2)
+ * with the viewpoint v and p = P_i; orient 2: dot = (n_0 g_0 + n_1 g_1) + n_2 g_2 with g = guide[i]; negate iff dot < 0.  orient
+ * 0, and where the dot is 0 or not finite: negate iff the component of largest magnitude -- the lowest axis on a tie -- is < 0.
+ * Every + - * / sqrt is correctly rounded float64 without contraction (what numpy float64 does): all outputs equal the
+ * restatement (tests/normals_ref.py) in every bit, at every grid, run after run.  A NaN entry of C is written as 0x7ff8000000000000.
+ * `grid` is the thinning's and changes the time only.  n_points = 0 writes nothing.  Blocks until the outputs are complete; the
+ * cloud (and the guide) must be complete on desc->stream's terms when the call is made.  Scratch (about 20 bytes per point and 4
+ * per cell) is allocated for the call and freed before it returns, on every error path too. */
+typedef struct gipuma_hip_normals_desc {
+    uint32_t abi_version; /* GIPUMA_HIP_ABI_VERSION */
+    int64_t n_points;     /* < 2^31; more: GIPUMA_HIP_ERR_UNSUPPORTED */
+    const float *points;  /* device pointer, packed xyz float32 */
+    float radius;         /* > 0 and finite, else GIPUMA_HIP_ERR_ARG */
+    int32_t k;            /* 3..32, else GIPUMA_HIP_ERR_ARG */
+    int32_t grid;         /* 0: automatic; 1..256: cells along the longest axis */
+    int32_t orient;       /* 0: largest component positive; 1: towards viewpoint; 2: along guide; else GIPUMA_HIP_ERR_ARG */
+    float viewpoint[3];   /* orient 1: finite, else GIPUMA_HIP_ERR_ARG; otherwise not read */
+    const float *guide;   /* orient 2: device pointer, n_points packed float32 normals, NULL: GIPUMA_HIP_ERR_ARG; otherwise not read */
+    int32_t device_id;    /* HIP device ordinal */
+    void *stream;         /* hipStream_t to launch on, NULL = one the library creates for the call */
+} gipuma_hip_normals_desc;
+
+/* normal_dev: 3 * n_points float32, device; variation_dev: n_points float32; count_dev: n_points uint32, m(i); scatter_dev:
+ * 6 * n_points float64, the upper triangle of C.  Each may be NULL, not all four where n_points > 0 (GIPUMA_HIP_ERR_ARG).
+ * info (points estimated; finite points short or degenerate; points not finite; estimated points whose normal was negated; cells
+ * along the longest axis, cells along x, y and z) and device_ms (HIP events around everything the call enqueues) may be NULL. */
+int gipuma_hip_cloud_normals(const gipuma_hip_normals_desc *desc, float *normal_dev, float *variation_dev, uint32_t *count_dev,
+                             double *scatter_dev, int64_t info[8], float *device_ms);
+
 #ifdef __cplusplus
 }
 #endif
